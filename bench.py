@@ -15,8 +15,19 @@ are fixed as N grows.
 
 Usage:
     python bench.py --gpus N --steps K --warmup W [--gb-per-gpu G]
+                    [--dump-outputs DIR] [--full]
 (N>1 is launched by the driver via torch.distributed.run; ranks read
 RANK/LOCAL_RANK/WORLD_SIZE/MASTER_* from the env.)
+
+A plain run does only what the headline figure needs: setup, warmup,
+the K timed steps, the result line.  --full adds the measurements that
+take runs of their own (today: the true-cold filter/join probes on the
+warmup steps, reported as config.*_cold_s; null without --full).
+
+--dump-outputs DIR writes what the last timed step's queries returned
+(the filter result and a fixed, seeded row sample of the join result)
+as DIR/<name>.npy in float64.  Inputs are seeded, so two builds run
+with the same arguments can be compared output for output.
 """
 
 import argparse
@@ -39,7 +50,16 @@ def main():
     ap.add_argument("--num-buckets", type=int, default=200)
     ap.add_argument("--device", default=None)
     ap.add_argument("--workdir", default=None)
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="write the last timed step's query outputs as "
+                         "DIR/<name>.npy")
+    ap.add_argument("--full", action="store_true",
+                    help="also run the true-cold query probes on the "
+                         "warmup steps")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be >= 1")
+    t_main = time.perf_counter()
 
     import torch
     import torch.distributed as dist
@@ -133,6 +153,8 @@ def main():
     if distributed:
         dist.barrier()
 
+    t_gen_done = time.perf_counter()
+
     session = hs.HyperspaceSession(device=device)
     session.conf.set(hs.IndexConstants.INDEX_NUM_BUCKETS, args.num_buckets)
     if os.environ.get("BENCH_GROUP_GB"):
@@ -161,9 +183,33 @@ def main():
         if distributed:
             dist.barrier()
 
+    def dump_outputs(out_dir, fout, jout):
+        # what a caller of the timed path receives from its last step:
+        # the filter and join result batches, rows in the order returned.
+        # A result above max_rows is cut to a fixed, seeded row sample
+        # (same rows every run for the same row count), which bounds the
+        # whole dump at 48 MiB of float64.
+        import numpy as np
+        max_rows = (48 << 20) // (8 * (len(fout.names) + len(jout.names)))
+        os.makedirs(out_dir, exist_ok=True)
+        for prefix, batch in (("filter", fout), ("join", jout)):
+            n = batch.num_rows
+            idx = None
+            if n > max_rows:
+                idx = torch.from_numpy(np.sort(np.random.default_rng(
+                    20240).integers(0, n, max_rows)))
+            for name in batch.names:
+                t = batch.tensor(name)
+                if idx is not None:
+                    t = t[idx.to(t.device)]
+                np.save(os.path.join(out_dir, f"{prefix}_{name}.npy"),
+                        t.cpu().numpy().astype(np.float64))
+        np.save(os.path.join(out_dir, "num_rows.npy"),
+                np.array([fout.num_rows, jout.num_rows], dtype=np.float64))
+
     filter_lat = []
     join_lat = []
-    cold_lat = []  # true-cold (f, j) probes from untimed warmup steps
+    cold_lat = []  # true-cold (f, j) probes from --full warmup steps
     build_times = []
     # index deletion is bookkeeping outside the benchmarked workload
     # (build + queries); it runs after the timed region unless keeping
@@ -207,7 +253,7 @@ def main():
         # still resident (the HBM cache holds the just-sorted batch)
         fout, f_post = run_query(fq)
 
-        if not timed:
+        if args.full and not timed:
             # TRUE cold, measured on UNTIMED warmup steps so the timed
             # workload stays build + serve: drop the HBM index-data
             # cache and the writer's layout cache, re-read + re-decode
@@ -260,20 +306,45 @@ def main():
             print(f"[dbg] build={t1-t0:.3f} queries={t6-t1:.3f} "
                   f"(f {f_post:.4f}/{f_warm:.4f} j {j_cold2:.4f}/"
                   f"{j_warm:.4f}) cleanup={t7-t6:.3f}", file=sys.stderr)
-        return fout.num_rows, jout.num_rows, has_index_join
+        return fout, jout, has_index_join
 
     # warmup
+    t_setup_done = time.perf_counter()
     for w in range(args.warmup):
         one_step(f"w{w}", timed=False)
     sync()
     t_start = time.perf_counter()
     for k in range(args.steps):
-        one_step(f"s{k}", timed=True)
+        outs = one_step(f"s{k}", timed=True)
+        if k < args.steps - 1:
+            # only the last step's results outlive their step: earlier
+            # ones are released before the next build, as a caller would
+            del outs
     sync()
     t_end = time.perf_counter()
 
-    for name in pending_cleanup:
-        h.vacuum_index(name)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, outs[0], outs[1])
+
+    t_dumped = time.perf_counter()
+    if distributed:
+        # vacuum is a rank-ordered collective here: keep it sequential
+        for name in pending_cleanup:
+            h.vacuum_index(name)
+    elif pending_cleanup:
+        # each version is its own index directory and log, and freeing
+        # their pages is kernel time with the GIL released: deleting the
+        # versions side by side takes a fraction of one-by-one
+        from concurrent.futures import ThreadPoolExecutor
+        with ThreadPoolExecutor(max_workers=8) as pool:
+            list(pool.map(h.vacuum_index, pending_cleanup))
+    if rank == 0 and os.environ.get("BENCH_DEBUG"):
+        print(f"[dbg] setup={t_setup_done-t_main:.1f}s "
+              f"(datagen {t_gen_done-t_main:.1f}s) "
+              f"warmup={t_start-t_setup_done:.1f}s "
+              f"timed={t_end-t_start:.1f}s dump={t_dumped-t_end:.1f}s "
+              f"deferred_vacuum={time.perf_counter()-t_dumped:.1f}s",
+              file=sys.stderr)
 
     elapsed = t_end - t_start
     # max over ranks

@@ -73,9 +73,9 @@ class Action(ABC):
         rank0 = dc.get_rank() == 0
         dc.barrier()
         if rank0:
-            self.validate()
             base = self.log_manager.get_latest_id()
             self.base_id = base if base is not None else -1
+            self.validate()
             self.begin()
         dc.barrier()
         no_changes = False
@@ -108,9 +108,14 @@ class Action(ABC):
         dc.barrier()
 
     def _run_local(self) -> None:
-        self.validate()
+        # base id is read BEFORE validate (the reference fixes baseId at
+        # construction, actions/Action.scala:35): an action that completes
+        # between our validate and the claim has then taken base+1/base+2,
+        # so the claim fails instead of stacking on a state we never
+        # validated against
         base = self.log_manager.get_latest_id()
         self.base_id = base if base is not None else -1
+        self.validate()
         try:
             self.begin()
             self.op()

@@ -2,7 +2,7 @@
 rows (the build's bucket-gather shape), V4-ILP vs the 1-elem
 grid-stride reference (HS_GATHER_V1=1)."""
 import os, sys, time
-sys.path.insert(0, "/root/repo")
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch
 from hyperspace_amd.ops import native
 

@@ -1,5 +1,5 @@
 import os, sys, time, tempfile
-sys.path.insert(0, "/root/repo")
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import numpy as np, pyarrow as pa, pyarrow.parquet as pq, torch
 from hyperspace_amd.sources.parquet_io import read_files_batch_device
 

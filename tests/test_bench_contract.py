@@ -36,6 +36,56 @@ def test_bench_json_contract(tmp_path):
         assert key in cfg, key
 
 
+def _run_bench(tmp_path, tag, *extra):
+    repo = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    dump = tmp_path / f"dump_{tag}"
+    out = subprocess.run(
+        [sys.executable, os.path.join(repo, "bench.py"),
+         "--device", "cpu", "--gb-per-gpu", "0.02",
+         "--steps", "2", "--warmup", "1",
+         "--workdir", str(tmp_path / f"w_{tag}"),
+         "--dump-outputs", str(dump), *extra],
+        capture_output=True, text=True, timeout=600,
+        env=dict(os.environ), cwd=repo)
+    assert out.returncode == 0, out.stderr[-2000:]
+    return json.loads(out.stdout.strip().splitlines()[-1]), dump
+
+
+def test_bench_plain_vs_full_and_dumped_outputs(tmp_path):
+    """A plain run skips the true-cold probes (null in the result line);
+    --full runs them.  --dump-outputs writes the last timed step's query
+    results as float64 .npy, identical from run to run, <= 64 MB."""
+    import numpy as np
+    plain, d_plain = _run_bench(tmp_path, "plain")
+    full, d_full = _run_bench(tmp_path, "full", "--full")
+    for d in (plain, full):
+        assert d["steps"] == 2 and d["warmup"] == 1
+        assert d["value"] > 0 and d["ms_per_step"] > 0
+    assert plain["config"]["filter_query_cold_s"] is None
+    assert plain["config"]["join_query_cold_s"] is None
+    assert full["config"]["filter_query_cold_s"] > 0
+    assert full["config"]["join_query_cold_s"] > 0
+
+    names = sorted(os.listdir(d_plain))
+    assert names == sorted(os.listdir(d_full))
+    for want in ("filter_key.npy", "filter_val.npy", "join_key.npy",
+                 "join_val.npy", "join_status.npy", "num_rows.npy"):
+        assert want in names, names
+    total = 0
+    for n in names:
+        a = np.load(d_plain / n)
+        assert a.dtype == np.float64, (n, a.dtype)
+        assert np.array_equal(a, np.load(d_full / n)), n
+        total += a.nbytes
+    assert total <= 64 * 1000 * 1000
+    n_filter, n_join = np.load(d_plain / "num_rows.npy")
+    fkey = np.load(d_plain / "filter_key.npy")
+    assert len(fkey) == n_filter > 0 and (fkey == 4242).all()
+    assert n_join > 0
+    assert len(np.load(d_plain / "join_key.npy")) == min(
+        n_join, 48 * 2**20 // (8 * (len(names) - 1)))
+
+
 def test_bench_forces_inline_cleanup_on_long_runs(tmp_path):
     """Long benchmark runs must vacuum each step's index inline —
     deferring tens of per-step versions to the end exhausts tmpfs/RAM

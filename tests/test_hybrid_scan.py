@@ -175,11 +175,13 @@ def test_hybrid_scan_delta_append_and_delete(tmp_path, monkeypatch):
     df = session.read_delta(str(tmp_path / "t"))
     h.create_index(df, hs.CoveringIndexConfig("hdx", ["key"], ["val"]))
 
-    # append one more file + delete one original THROUGH THE DELTA LOG
+    # append one more file + delete one original THROUGH THE DELTA LOG;
+    # the victim is picked before the append: data file names are random,
+    # so the first file of the later listing may be the appended one
+    victim = t.files_at()[0].name
     t.append_batch(ColumnBatch({
         "key": torch.from_numpy(rng.integers(0, 1000, 1000)),
         "val": torch.from_numpy(rng.random(1000))}))
-    victim = t.files_at()[0].name
     t.remove_files([victim])
 
     session.enable_hyperspace()
