@@ -156,12 +156,20 @@ std::tuple<torch::Tensor, torch::Tensor> radix_sort_pairs(
   return {out_keys, out_payload};
 }
 
+// mode: hsk::MergeJoinMode (0 inner, 1 left outer, 2 left semi, 3 left
+// anti).  Semi and anti return an empty second tensor.
 std::tuple<torch::Tensor, torch::Tensor> merge_join(torch::Tensor lkeys,
                                                     torch::Tensor rkeys,
                                                     torch::Tensor lseg,
-                                                    torch::Tensor rseg) {
+                                                    torch::Tensor rseg,
+                                                    int64_t mode) {
   check_cuda(lkeys, "lkeys");
   check_cuda(rkeys, "rkeys");
+  TORCH_CHECK(mode >= hsk::MERGE_JOIN_INNER &&
+                  mode <= hsk::MERGE_JOIN_LEFT_ANTI,
+              "merge_join: unknown mode ", mode);
+  bool pairs = mode == hsk::MERGE_JOIN_INNER ||
+               mode == hsk::MERGE_JOIN_LEFT_OUTER;
   auto dev = lkeys.device();
   auto opts = torch::dtype(torch::kInt64).device(dev);
   // segment offsets may arrive on CPU
@@ -170,8 +178,17 @@ std::tuple<torch::Tensor, torch::Tensor> merge_join(torch::Tensor lkeys,
   int64_t n_left = lkeys.numel();
   int64_t n_seg = lseg_d.numel() - 1;
   auto stream = current_stream();
-  if (n_left == 0 || rkeys.numel() == 0) {
+  if (n_left == 0) {
     return {torch::empty({0}, opts), torch::empty({0}, opts)};
+  }
+  if (rkeys.numel() == 0) {
+    // nothing can match: inner and semi are empty, outer and anti keep
+    // every left row (null-extended for outer) without a launch
+    if (mode == hsk::MERGE_JOIN_INNER || mode == hsk::MERGE_JOIN_LEFT_SEMI)
+      return {torch::empty({0}, opts), torch::empty({0}, opts)};
+    return {torch::arange(n_left, opts),
+            pairs ? torch::full({n_left}, -1, opts)
+                  : torch::empty({0}, opts)};
   }
   int64_t tile = hsk::merge_join_tile_size();
   int64_t n_tiles = (n_left + tile - 1) / tile;
@@ -180,7 +197,8 @@ std::tuple<torch::Tensor, torch::Tensor> merge_join(torch::Tensor lkeys,
                              (const uint64_t*)rkeys.data_ptr<int64_t>(),
                              lseg_d.data_ptr<int64_t>(),
                              rseg_d.data_ptr<int64_t>(), n_left, n_seg,
-                             tile_counts.data_ptr<int64_t>(), stream);
+                             (int)mode, tile_counts.data_ptr<int64_t>(),
+                             stream);
   auto tile_offsets = torch::empty({n_tiles}, opts);
   auto total = torch::empty({1}, opts);
   hsk::exclusive_scan_i64(tile_counts.data_ptr<int64_t>(),
@@ -188,15 +206,16 @@ std::tuple<torch::Tensor, torch::Tensor> merge_join(torch::Tensor lkeys,
                           total.data_ptr<int64_t>(), stream);
   int64_t n_out = total.cpu().item<int64_t>();
   auto out_l = torch::empty({n_out}, opts);
-  auto out_r = torch::empty({n_out}, opts);
+  auto out_r = torch::empty({pairs ? n_out : 0}, opts);
   if (n_out > 0) {
     hsk::merge_join_tile_emit((const uint64_t*)lkeys.data_ptr<int64_t>(),
                               (const uint64_t*)rkeys.data_ptr<int64_t>(),
                               lseg_d.data_ptr<int64_t>(),
                               rseg_d.data_ptr<int64_t>(), n_left, n_seg,
-                              tile_offsets.data_ptr<int64_t>(),
+                              (int)mode, tile_offsets.data_ptr<int64_t>(),
                               out_l.data_ptr<int64_t>(),
-                              out_r.data_ptr<int64_t>(), stream);
+                              pairs ? out_r.data_ptr<int64_t>() : nullptr,
+                              stream);
   }
   return {out_l, out_r};
 }
@@ -654,7 +673,9 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("masks") = std::vector<torch::Tensor>{});
   m.def("normalize_key", &normalize_key, "order-preserving u64 key");
   m.def("radix_sort_pairs", &radix_sort_pairs, "stable LSD radix sort");
-  m.def("merge_join", &merge_join, "segmented sorted merge join");
+  m.def("merge_join", &merge_join, "segmented sorted merge join",
+        py::arg("lkeys"), py::arg("rkeys"), py::arg("lseg"), py::arg("rseg"),
+        py::arg("mode") = 0);
   m.def("select_range_u64", &select_range_u64_pub, "range filter compaction");
   m.def("isin_sorted", &isin_sorted, "sorted-set membership");
   m.def("segmented_minmax", &segmented_minmax, "per-segment min/max");

@@ -54,6 +54,27 @@ void merge_join_tile_emit(const uint64_t* lkeys, const uint64_t* rkeys,
                           int64_t n_left, int64_t n_seg,
                           const int64_t* tile_offsets, int64_t* out_l,
                           int64_t* out_r, hipStream_t stream);
+// Join modes of the tile join (compile-time instantiations of the same
+// two kernels).  With c = a left row's match count, the row takes
+// e slots: INNER c; LEFT_OUTER max(c, 1), the single pair (i, -1) when
+// c == 0; LEFT_SEMI c > 0; LEFT_ANTI c == 0.  tile_counts hold sums of
+// e.  Semi and anti write only out_l (out_r may be null).  The overloads
+// without ``mode`` above are the INNER join.
+enum MergeJoinMode : int {
+  MERGE_JOIN_INNER = 0,
+  MERGE_JOIN_LEFT_OUTER = 1,
+  MERGE_JOIN_LEFT_SEMI = 2,
+  MERGE_JOIN_LEFT_ANTI = 3,
+};
+void merge_join_tile_count(const uint64_t* lkeys, const uint64_t* rkeys,
+                           const int64_t* lseg, const int64_t* rseg,
+                           int64_t n_left, int64_t n_seg, int mode,
+                           int64_t* tile_counts, hipStream_t stream);
+void merge_join_tile_emit(const uint64_t* lkeys, const uint64_t* rkeys,
+                          const int64_t* lseg, const int64_t* rseg,
+                          int64_t n_left, int64_t n_seg, int mode,
+                          const int64_t* tile_offsets, int64_t* out_l,
+                          int64_t* out_r, hipStream_t stream);
 
 // generic exclusive scan over i64 (single pass, device-wide)
 void exclusive_scan_i64(const int64_t* in, int64_t* out, int64_t n,

@@ -767,12 +767,41 @@ __device__ __forceinline__ void mj_tile_narrow(
 // per-row probes hit LDS instead of chasing L2/HBM latency
 #define MJ_LDS_WIN 2048
 
+// Join modes: a compile-time parameter of both phases.  Each searched
+// left row has a right start ``a`` and a match count ``c``; the mode only
+// changes how many output slots ``e`` the row takes and what goes in them:
+//   INNER       e = c            (i, a+j) for j < c
+//   LEFT_OUTER  e = max(c, 1)    the inner pairs, or (i, -1) when c == 0
+//   LEFT_SEMI   e = c > 0        i once (out_l only)
+//   LEFT_ANTI   e = c == 0       i once (out_l only)
+// Tile totals and the intra-tile prefix are sums of ``e``, so output
+// stays ascending by left row and an unmatched outer row sits exactly
+// in its place.  The values mirror MergeJoinMode in kernels.h.
+#define MJ_INNER 0
+#define MJ_LEFT_OUTER 1
+#define MJ_LEFT_SEMI 2
+#define MJ_LEFT_ANTI 3
+
+template <int MODE>
+__device__ __forceinline__ int64_t mj_emit_count(int64_t c) {
+  if constexpr (MODE == MJ_LEFT_OUTER) return c > 0 ? c : 1;
+  if constexpr (MODE == MJ_LEFT_SEMI) return c > 0 ? 1 : 0;
+  if constexpr (MODE == MJ_LEFT_ANTI) return c == 0 ? 1 : 0;
+  return c;
+}
+
 // fill this thread's MJ_RPT consecutive rows: one binary search for the
 // first row, forward-monotone searches for the rest (keys ascend, so
 // each row's range starts at or after the previous row's).
 // ``rbase``/``r_base_off``: the searched array and the global offset of
 // its element 0 — (lwin, tile_lo) when the window is LDS-staged, else
 // (rkeys, 0); a_out entries are global right indices either way.
+// Returns the thread's emitted-slot total (sum of e).  c_out holds the
+// raw match counts; a skipped row (past n_left or the tile's segment
+// end) is not an unmatched row and takes no slot in any mode: INNER
+// marks it c = 0 as before, the other modes mark it c = -1 so the emit
+// phase can tell it from a searched row with no match.
+template <int MODE>
 __device__ __forceinline__ int64_t mj_thread_rows(
     const uint64_t* __restrict__ lkeys, const uint64_t* __restrict__ rbase,
     int64_t r_base_off, const int64_t* __restrict__ lseg,
@@ -785,7 +814,7 @@ __device__ __forceinline__ int64_t mj_thread_rows(
   for (int k = 0; k < MJ_RPT; k++) {
     int64_t i = first + k;
     if (i >= n_left || (tile_seg >= 0 && i >= lseg[tile_seg + 1])) {
-      c_out[k] = 0;
+      c_out[k] = MODE == MJ_INNER ? 0 : -1;
       continue;
     }
     if (tile_seg < 0) {
@@ -801,7 +830,7 @@ __device__ __forceinline__ int64_t mj_thread_rows(
     int64_t b = upper_bound_u64(rbase, a, r1, key);
     a_out[k] = a + r_base_off;
     c_out[k] = b - a;
-    total += b - a;
+    total += mj_emit_count<MODE>(b - a);
     a_prev = a;
   }
   return total;
@@ -822,6 +851,7 @@ __device__ __forceinline__ bool mj_stage_window(
   return use_lds;
 }
 
+template <int MODE>
 __global__ void k_mj_tile_count(const uint64_t* __restrict__ lkeys,
                                 const uint64_t* __restrict__ rkeys,
                                 const int64_t* __restrict__ lseg,
@@ -841,7 +871,7 @@ __global__ void k_mj_tile_count(const uint64_t* __restrict__ lkeys,
     bool use_lds = mj_stage_window(rkeys, lwin, tile_seg, tile_lo,
                                    tile_hi);
     int64_t a_arr[MJ_RPT], c_arr[MJ_RPT];
-    red[threadIdx.x] = mj_thread_rows(
+    red[threadIdx.x] = mj_thread_rows<MODE>(
         lkeys, use_lds ? lwin : rkeys, use_lds ? tile_lo : 0, lseg, rseg,
         n_left, n_seg, base + (int64_t)threadIdx.x * MJ_RPT, tile_seg,
         tile_lo, tile_hi, a_arr, c_arr);
@@ -855,6 +885,7 @@ __global__ void k_mj_tile_count(const uint64_t* __restrict__ lkeys,
   }
 }
 
+template <int MODE>
 __global__ void k_mj_tile_emit(const uint64_t* __restrict__ lkeys,
                                const uint64_t* __restrict__ rkeys,
                                const int64_t* __restrict__ lseg,
@@ -876,7 +907,7 @@ __global__ void k_mj_tile_emit(const uint64_t* __restrict__ lkeys,
     bool use_lds = mj_stage_window(rkeys, lwin, tile_seg, tile_lo,
                                    tile_hi);
     int64_t a_arr[MJ_RPT], c_arr[MJ_RPT];
-    int64_t my_total = mj_thread_rows(
+    int64_t my_total = mj_thread_rows<MODE>(
         lkeys, use_lds ? lwin : rkeys, use_lds ? tile_lo : 0, lseg, rseg,
         n_left, n_seg, base + (int64_t)threadIdx.x * MJ_RPT, tile_seg,
         tile_lo, tile_hi, a_arr, c_arr);
@@ -892,10 +923,30 @@ __global__ void k_mj_tile_emit(const uint64_t* __restrict__ lkeys,
     int64_t off_out = tile_offsets[tile] + pfx[threadIdx.x] - my_total;
     for (int k = 0; k < MJ_RPT; k++) {
       int64_t i = base + (int64_t)threadIdx.x * MJ_RPT + k;
-      for (int64_t j = 0; j < c_arr[k]; j++) {
-        out_l[off_out] = i;
-        out_r[off_out] = a_arr[k] + j;
-        off_out++;
+      if constexpr (MODE == MJ_INNER) {
+        for (int64_t j = 0; j < c_arr[k]; j++) {
+          out_l[off_out] = i;
+          out_r[off_out] = a_arr[k] + j;
+          off_out++;
+        }
+      } else {
+        int64_t c = c_arr[k];
+        if (c < 0) continue;  // skipped row: no slot
+        if constexpr (MODE == MJ_LEFT_OUTER) {
+          if (c == 0) {
+            out_l[off_out] = i;
+            out_r[off_out] = -1;
+            off_out++;
+          }
+          for (int64_t j = 0; j < c; j++) {
+            out_l[off_out] = i;
+            out_r[off_out] = a_arr[k] + j;
+            off_out++;
+          }
+        } else {
+          // semi / anti: out_r is not written (may be null)
+          if ((MODE == MJ_LEFT_SEMI) == (c > 0)) out_l[off_out++] = i;
+        }
       }
     }
     __syncthreads();
@@ -940,14 +991,50 @@ void run_merge_perm(const uint64_t* keys, const int64_t* seg,
                      0, stream, keys, seg, split, n, n_seg, perm);
 }
 
+// one launch per mode: the mode is a template argument, so the INNER
+// instantiation carries no per-row mode test
+#define MJ_DISPATCH(mode, LAUNCH)          \
+  switch (mode) {                          \
+    case MJ_INNER: LAUNCH(MJ_INNER); break;            \
+    case MJ_LEFT_OUTER: LAUNCH(MJ_LEFT_OUTER); break;  \
+    case MJ_LEFT_SEMI: LAUNCH(MJ_LEFT_SEMI); break;    \
+    case MJ_LEFT_ANTI: LAUNCH(MJ_LEFT_ANTI); break;    \
+    default: break;                        \
+  }
+
+void merge_join_tile_count(const uint64_t* lkeys, const uint64_t* rkeys,
+                           const int64_t* lseg, const int64_t* rseg,
+                           int64_t n_left, int64_t n_seg, int mode,
+                           int64_t* tile_counts, hipStream_t stream) {
+  if (n_left == 0) return;
+#define MJ_LAUNCH_COUNT(M)                                               \
+  hipLaunchKernelGGL(k_mj_tile_count<M>, dim3(grid_for(n_left)),         \
+                     dim3(THREADS), 0, stream, lkeys, rkeys, lseg, rseg, \
+                     n_left, n_seg, tile_counts)
+  MJ_DISPATCH(mode, MJ_LAUNCH_COUNT)
+#undef MJ_LAUNCH_COUNT
+}
+
 void merge_join_tile_count(const uint64_t* lkeys, const uint64_t* rkeys,
                            const int64_t* lseg, const int64_t* rseg,
                            int64_t n_left, int64_t n_seg,
                            int64_t* tile_counts, hipStream_t stream) {
+  merge_join_tile_count(lkeys, rkeys, lseg, rseg, n_left, n_seg, MJ_INNER,
+                        tile_counts, stream);
+}
+
+void merge_join_tile_emit(const uint64_t* lkeys, const uint64_t* rkeys,
+                          const int64_t* lseg, const int64_t* rseg,
+                          int64_t n_left, int64_t n_seg, int mode,
+                          const int64_t* tile_offsets, int64_t* out_l,
+                          int64_t* out_r, hipStream_t stream) {
   if (n_left == 0) return;
-  hipLaunchKernelGGL(k_mj_tile_count, dim3(grid_for(n_left)), dim3(THREADS),
-                     0, stream, lkeys, rkeys, lseg, rseg, n_left, n_seg,
-                     tile_counts);
+#define MJ_LAUNCH_EMIT(M)                                                \
+  hipLaunchKernelGGL(k_mj_tile_emit<M>, dim3(grid_for(n_left)),          \
+                     dim3(THREADS), 0, stream, lkeys, rkeys, lseg, rseg, \
+                     n_left, n_seg, tile_offsets, out_l, out_r)
+  MJ_DISPATCH(mode, MJ_LAUNCH_EMIT)
+#undef MJ_LAUNCH_EMIT
 }
 
 void merge_join_tile_emit(const uint64_t* lkeys, const uint64_t* rkeys,
@@ -955,11 +1042,10 @@ void merge_join_tile_emit(const uint64_t* lkeys, const uint64_t* rkeys,
                           int64_t n_left, int64_t n_seg,
                           const int64_t* tile_offsets, int64_t* out_l,
                           int64_t* out_r, hipStream_t stream) {
-  if (n_left == 0) return;
-  hipLaunchKernelGGL(k_mj_tile_emit, dim3(grid_for(n_left)), dim3(THREADS),
-                     0, stream, lkeys, rkeys, lseg, rseg, n_left, n_seg,
-                     tile_offsets, out_l, out_r);
+  merge_join_tile_emit(lkeys, rkeys, lseg, rseg, n_left, n_seg, MJ_INNER,
+                       tile_offsets, out_l, out_r, stream);
 }
+#undef MJ_DISPATCH
 
 // ---------------------------------------------------------------------------
 // Filter scan: stable compaction of rows in a u64 range (select_range)

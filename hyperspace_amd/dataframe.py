@@ -33,6 +33,16 @@ class DataFrame:
 
     def join(self, other: "DataFrame", on: Union[str, Expr, List[str]],
              how: str = "inner") -> "DataFrame":
+        """Equi-join with ``other``.
+
+        ``how`` is one of (case-insensitive):
+        ``inner``; ``left`` / ``left_outer`` / ``leftouter``;
+        ``right`` / ``right_outer`` / ``rightouter``;
+        ``full`` / ``outer`` / ``full_outer`` / ``fullouter``;
+        ``semi`` / ``left_semi`` / ``leftsemi``;
+        ``anti`` / ``left_anti`` / ``leftanti``.
+        Outer joins null-extend the unmatched side; semi and anti return
+        only this frame's columns.  Null join keys never match."""
         if isinstance(on, str):
             on = [on]
         if isinstance(on, list):

@@ -512,6 +512,11 @@ class Executor:
         lbatch, lseg = self._exec(plan.left)
         rbatch, rseg = self._exec(plan.right)
 
+        if plan.join_type != "inner":
+            return self._exec_typed_join(
+                plan.join_type, pairs, lbatch, lseg, rbatch, rseg,
+                left_bucketed and right_bucketed)
+
         # inner-join SQL semantics: null join keys never match — drop
         # them up front (bucketed layouts keep NULLS FIRST per bucket,
         # so the segment offsets shift by the per-prefix null count)
@@ -551,34 +556,83 @@ class Executor:
 
         # secondary key equality check for multi-key joins (null
         # secondary keys never match)
-        if len(pairs) > 1 and lidx.numel():
-            keep = torch.ones(lidx.numel(), dtype=torch.bool,
-                              device=lidx.device)
-            for ln, rn in pairs[1:]:
-                lv_t, rv_t = _join_key_tensors(lbatch, rbatch, ln, rn)
-                keep &= (lv_t[lidx] == rv_t[ridx])
-                lm, rm = lbatch.mask(ln), rbatch.mask(rn)
-                if lm is not None:
-                    keep &= lm[lidx]
-                if rm is not None:
-                    keep &= rm[ridx]
-            sel = torch.nonzero(keep, as_tuple=False).flatten()
-            lidx, ridx = lidx[sel], ridx[sel]
+        lidx, ridx = _secondary_key_filter(lbatch, rbatch, pairs, lidx, ridx)
+        return _join_columns(lbatch.gather(lidx), rbatch.gather(ridx))
 
-        lout = lbatch.gather(lidx)
-        rout = rbatch.gather(ridx)
-        cols: Dict[str, object] = {}
-        masks: Dict[str, torch.Tensor] = {}
-        for k, v in lout.columns.items():
-            cols[k] = v
-            if lout.mask(k) is not None:
-                masks[k] = lout.mask(k)
-        for k, v in rout.columns.items():
-            name = k if k not in cols else f"{k}_r"
-            cols[name] = v
-            if rout.mask(k) is not None:
-                masks[name] = rout.mask(k)
-        return ColumnBatch(cols, masks)
+    def _exec_typed_join(self, jt: str, pairs, lbatch: ColumnBatch,
+                         lseg: Optional[torch.Tensor], rbatch: ColumnBatch,
+                         rseg: Optional[torch.Tensor], both_bucketed: bool
+                         ) -> ColumnBatch:
+        """Outer, semi and anti joins (``jt`` is the canonical type).
+
+        Same two physical paths as the inner join; the merge-join kernel
+        runs in the matching mode.  Null join keys never match: such
+        rows leave the kernel's input, and those of a preserved side come
+        back as unmatched rows.  A right outer join is the left outer
+        join of the swapped sides; a full outer join is left_outer(L, R)
+        plus the rows of left_anti(R, L) with null left columns — both
+        sides are sorted and co-segmented, so the swap is valid on either
+        path."""
+        lkey, rkey = pairs[0]
+        lbatch, lseg, lnull = _split_null_keys(lbatch, lkey, lseg)
+        rbatch, rseg, rnull = _split_null_keys(rbatch, rkey, rseg)
+        lk_t, rk_t = _join_key_tensors(lbatch, rbatch, lkey, rkey)
+        lk = ops.normalize_key(lk_t)
+        rk = ops.normalize_key(rk_t)
+        if (both_bucketed and lseg is not None and rseg is not None
+                and lseg.numel() == rseg.numel()):
+            self.stats.merge_joins += 1
+            self.stats.record(f"SortMergeJoin(co-bucketed, {jt})")
+        else:
+            self.stats.shuffles += 2
+            self.stats.hash_joins += 1
+            self.stats.record(f"SortMergeJoin(shuffled, {jt})")
+            if lk.numel():
+                lperm = ops.sort_perm(lk)
+                lbatch, lk = lbatch.gather(lperm), lk[lperm]
+            if rk.numel():
+                rperm = ops.sort_perm(rk)
+                rbatch, rk = rbatch.gather(rperm), rk[rperm]
+            lseg = torch.tensor([0, lk.numel()], dtype=torch.int64)
+            rseg = torch.tensor([0, rk.numel()], dtype=torch.int64)
+        rpairs = [(r, l) for l, r in pairs]
+
+        def from_left(mode):
+            return _typed_match(mode, lk, rk, lseg, rseg, lbatch, rbatch,
+                                pairs)
+
+        def from_right(mode):
+            return _typed_match(mode, rk, lk, rseg, lseg, rbatch, lbatch,
+                                rpairs)
+
+        if jt == "left_semi":
+            return lbatch.gather(from_left("left_semi")[0])
+        if jt == "left_anti":
+            out = lbatch.gather(from_left("left_anti")[0])
+            return out if lnull is None else ColumnBatch.concat([out, lnull])
+
+        # (left part, right part) row-aligned pieces of the result
+        pieces: List[Tuple[ColumnBatch, ColumnBatch]] = []
+        if jt in ("left_outer", "full_outer"):
+            lidx, ridx = from_left("left_outer")
+            pieces.append((lbatch.gather(lidx),
+                           _gather_nullable(rbatch, ridx)))
+            if lnull is not None:
+                pieces.append((lnull, _null_batch(rbatch, lnull.num_rows)))
+            if jt == "full_outer":
+                ranti = from_right("left_anti")[0]
+                pieces.append((_null_batch(lbatch, ranti.numel()),
+                               rbatch.gather(ranti)))
+        else:  # right_outer
+            ridx, lidx = from_right("left_outer")
+            pieces.append((_gather_nullable(lbatch, lidx),
+                           rbatch.gather(ridx)))
+        if jt in ("right_outer", "full_outer") and rnull is not None:
+            pieces.append((_null_batch(lbatch, rnull.num_rows), rnull))
+        if len(pieces) == 1:
+            return _join_columns(*pieces[0])
+        return _join_columns(ColumnBatch.concat([p[0] for p in pieces]),
+                             ColumnBatch.concat([p[1] for p in pieces]))
 
     # ------------------------------------------------------------------
     def _exec_bucket_union(self, plan: BucketUnionNode
@@ -698,6 +752,117 @@ def _drop_null_keys(batch: ColumnBatch, key_name: str,
             torch.cumsum((~m).to(torch.int64), 0)])
         seg = (seg.to(m.device) - nullcum[seg.to(m.device)]).cpu()
     return batch.gather(keep), seg
+
+
+def _split_null_keys(batch: ColumnBatch, key_name: str,
+                     seg: Optional[torch.Tensor]
+                     ) -> Tuple[ColumnBatch, Optional[torch.Tensor],
+                                Optional[ColumnBatch]]:
+    """``_drop_null_keys`` that also returns the null-key rows (None when
+    there are none) so an outer or anti join can keep them as unmatched."""
+    if not batch.has_nulls(key_name):
+        return batch, seg, None
+    nulls = batch.gather(torch.nonzero(
+        ~batch.mask(key_name), as_tuple=False).flatten())
+    kept, seg = _drop_null_keys(batch, key_name, seg)
+    return kept, seg, nulls
+
+
+def _secondary_key_filter(lbatch: ColumnBatch, rbatch: ColumnBatch, pairs,
+                          lidx: torch.Tensor, ridx: torch.Tensor
+                          ) -> Tuple[torch.Tensor, torch.Tensor]:
+    """Secondary key equality check for multi-key joins over the
+    primary-key pairs (null secondary keys never match)."""
+    if len(pairs) > 1 and lidx.numel():
+        keep = torch.ones(lidx.numel(), dtype=torch.bool,
+                          device=lidx.device)
+        for ln, rn in pairs[1:]:
+            lv_t, rv_t = _join_key_tensors(lbatch, rbatch, ln, rn)
+            keep &= (lv_t[lidx] == rv_t[ridx])
+            lm, rm = lbatch.mask(ln), rbatch.mask(rn)
+            if lm is not None:
+                keep &= lm[lidx]
+            if rm is not None:
+                keep &= rm[ridx]
+        sel = torch.nonzero(keep, as_tuple=False).flatten()
+        lidx, ridx = lidx[sel], ridx[sel]
+    return lidx, ridx
+
+
+def _typed_match(mode: str, lk: torch.Tensor, rk: torch.Tensor,
+                 lseg: torch.Tensor, rseg: torch.Tensor,
+                 lbatch: ColumnBatch, rbatch: ColumnBatch, pairs
+                 ) -> Tuple[torch.Tensor, torch.Tensor]:
+    """(lidx, ridx) of a left_outer / left_semi / left_anti match.
+
+    A single-key join is one fused kernel pass in that mode.  With
+    secondary keys the kernel cannot see that all of a row's primary
+    matches fail the secondary check, so the inner pairs are filtered
+    first and the result is derived from the surviving left rows (order
+    within the result is then matched rows first; none is promised)."""
+    if len(pairs) == 1:
+        return ops.merge_join(lk, rk, lseg, rseg, mode)
+    lidx, ridx = ops.merge_join(lk, rk, lseg, rseg)
+    lidx, ridx = _secondary_key_filter(lbatch, rbatch, pairs, lidx, ridx)
+    matched = torch.zeros(lbatch.num_rows, dtype=torch.bool,
+                          device=lk.device)
+    matched[lidx] = True
+    none = torch.empty(0, dtype=torch.int64, device=lk.device)
+    if mode == "left_semi":
+        return torch.nonzero(matched, as_tuple=False).flatten(), none
+    unmatched = torch.nonzero(~matched, as_tuple=False).flatten()
+    if mode == "left_anti":
+        return unmatched, none
+    return (torch.cat([lidx, unmatched]),
+            torch.cat([ridx, torch.full_like(unmatched, -1)]))
+
+
+def _null_batch(like: ColumnBatch, n: int) -> ColumnBatch:
+    """``n`` all-null rows with the columns and dtypes of ``like``.  The
+    value slots hold the fill a null carries elsewhere (0 / the first
+    dictionary entry, "" for an empty dictionary)."""
+    dev = like.device
+    cols: Dict[str, object] = {}
+    for k, v in like.columns.items():
+        if isinstance(v, StringColumn):
+            cols[k] = StringColumn(
+                torch.zeros(n, dtype=torch.int32, device=dev),
+                v.values if len(v.values) else [""])
+        else:
+            cols[k] = torch.zeros(n, dtype=v.dtype, device=dev)
+    return ColumnBatch(cols, {k: torch.zeros(n, dtype=torch.bool, device=dev)
+                              for k in cols})
+
+
+def _gather_nullable(batch: ColumnBatch, idx: torch.Tensor) -> ColumnBatch:
+    """Gather where ``idx == -1`` yields an all-null row.  The -1 never
+    reaches the gather: it is clamped to row 0 and masked out; a batch
+    with no rows to clamp to is built as nulls directly."""
+    if batch.num_rows == 0:
+        return _null_batch(batch, idx.numel())
+    out = batch.gather(idx.clamp_min(0))
+    valid = idx >= 0
+    masks = {}
+    for k in out.columns:
+        m = out.mask(k)
+        masks[k] = valid if m is None else (valid & m)
+    return ColumnBatch(out.columns, masks)
+
+
+def _join_columns(lout: ColumnBatch, rout: ColumnBatch) -> ColumnBatch:
+    """Left then right columns; a right name already taken gets ``_r``."""
+    cols: Dict[str, object] = {}
+    masks: Dict[str, torch.Tensor] = {}
+    for k, v in lout.columns.items():
+        cols[k] = v
+        if lout.mask(k) is not None:
+            masks[k] = lout.mask(k)
+    for k, v in rout.columns.items():
+        name = k if k not in cols else f"{k}_r"
+        cols[name] = v
+        if rout.mask(k) is not None:
+            masks[name] = rout.mask(k)
+    return ColumnBatch(cols, masks)
 
 
 def _empty_batch(schema) -> ColumnBatch:

@@ -97,11 +97,19 @@ def run_merge_perm(keys_u64: torch.Tensor, seg: torch.Tensor,
 
 
 def merge_join(lkeys: torch.Tensor, rkeys: torch.Tensor,
-               lseg: torch.Tensor, rseg: torch.Tensor
+               lseg: torch.Tensor, rseg: torch.Tensor,
+               mode: str = "inner"
                ) -> Tuple[torch.Tensor, torch.Tensor]:
+    """Segmented sorted merge join.  ``mode`` is one of ``"inner"``,
+    ``"left_outer"`` (an unmatched left row yields the pair (i, -1)),
+    ``"left_semi"`` and ``"left_anti"`` (left indices only; the second
+    tensor is empty).  Output is ascending by left row in every mode."""
+    code = cpu_ref.merge_join_mode_code(mode)
     if _is_cuda(lkeys, rkeys):
-        return native.ext().merge_join(lkeys, rkeys, lseg, rseg)
-    return cpu_ref.merge_join(lkeys, rkeys, lseg, rseg)
+        if code == 0:
+            return native.ext().merge_join(lkeys, rkeys, lseg, rseg)
+        return native.ext().merge_join(lkeys, rkeys, lseg, rseg, code)
+    return cpu_ref.merge_join(lkeys, rkeys, lseg, rseg, mode)
 
 
 def select_range_u64(keys_u64: torch.Tensor, lo: int, hi: int,

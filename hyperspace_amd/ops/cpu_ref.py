@@ -146,45 +146,82 @@ def sort_perm_u64(keys_u64: torch.Tensor) -> torch.Tensor:
 # Segmented sorted merge join (K4)
 # ---------------------------------------------------------------------------
 
+MERGE_JOIN_MODES = {"inner": 0, "left_outer": 1, "left_semi": 2,
+                    "left_anti": 3}
+
+
+def merge_join_mode_code(mode: str) -> int:
+    """Kernel mode code for a merge-join mode name."""
+    try:
+        return MERGE_JOIN_MODES[mode]
+    except KeyError:
+        raise ValueError(
+            f"merge_join mode {mode!r} not in {sorted(MERGE_JOIN_MODES)}")
+
+
 def merge_join(lkeys: torch.Tensor, rkeys: torch.Tensor,
-               lseg: torch.Tensor, rseg: torch.Tensor
+               lseg: torch.Tensor, rseg: torch.Tensor,
+               mode: str = "inner"
                ) -> Tuple[torch.Tensor, torch.Tensor]:
     """Join two segment-partitioned sorted key arrays.
 
     ``lseg``/``rseg`` are segment offset arrays of equal length S+1; segment
-    s spans [lseg[s], lseg[s+1]).  Keys are sorted within each segment.
+    s spans [lseg[s], lseg[s+1]).  Keys are u64 values stored in int64,
+    sorted in u64 order within each segment.
     Returns (left_idx, right_idx) global row-index pairs of all equal-key
     matches, segment-aligned (only same-segment rows join — this is the
     zero-exchange co-bucketed join).
+
+    With c = a left row's match count, ``mode`` selects how many output
+    slots e the row takes: ``inner`` c; ``left_outer`` max(c, 1), the
+    single pair (i, -1) when c == 0; ``left_semi`` c > 0; ``left_anti``
+    c == 0.  Semi and anti return an empty right_idx.  Output is
+    ascending by left row, a row's matches ascending by right index.
     """
     assert lseg.numel() == rseg.numel()
+    code = merge_join_mode_code(mode)
+    pairs = code in (0, 1)
     louts, routs = [], []
     S = lseg.numel() - 1
     for s in range(S):
         l0, l1 = int(lseg[s]), int(lseg[s + 1])
         r0, r1 = int(rseg[s]), int(rseg[s + 1])
-        if l1 <= l0 or r1 <= r0:
+        if l1 <= l0:
             continue
-        lk = lkeys[l0:l1]
-        rk = rkeys[r0:r1]
+        # an empty right segment searches to lo == hi == 0: every left
+        # row of the segment is unmatched
+        lk = _as_unsigned_sortable(lkeys[l0:l1]).contiguous()
+        rk = _as_unsigned_sortable(rkeys[r0:max(r0, r1)]).contiguous()
         lo = torch.searchsorted(rk, lk, side="left")
         hi = torch.searchsorted(rk, lk, side="right")
         counts = (hi - lo).clamp(min=0)
-        total = int(counts.sum())
+        if code == 0:
+            emit = counts
+        elif code == 1:
+            emit = counts.clamp(min=1)
+        elif code == 2:
+            emit = (counts > 0).to(torch.int64)
+        else:
+            emit = (counts == 0).to(torch.int64)
+        total = int(emit.sum())
         if total == 0:
             continue
-        lidx = torch.repeat_interleave(
-            torch.arange(l0, l1, dtype=torch.int64), counts)
-        starts = torch.repeat_interleave(lo, counts)
+        louts.append(torch.repeat_interleave(
+            torch.arange(l0, l1, dtype=torch.int64), emit))
+        if not pairs:
+            continue
+        starts = torch.repeat_interleave(lo, emit)
         offs = torch.arange(total, dtype=torch.int64) - \
-            torch.repeat_interleave(torch.cumsum(counts, 0) - counts, counts)
+            torch.repeat_interleave(torch.cumsum(emit, 0) - emit, emit)
         ridx = r0 + starts + offs
-        louts.append(lidx)
+        if code == 1:
+            matched = torch.repeat_interleave(counts, emit) > 0
+            ridx = torch.where(matched, ridx, torch.full_like(ridx, -1))
         routs.append(ridx)
+    e = torch.empty(0, dtype=torch.int64)
     if not louts:
-        e = torch.empty(0, dtype=torch.int64)
         return e, e.clone()
-    return torch.cat(louts), torch.cat(routs)
+    return torch.cat(louts), (torch.cat(routs) if pairs else e)
 
 
 # ---------------------------------------------------------------------------

@@ -127,14 +127,37 @@ class Project(LogicalPlan):
         return f"Project({self.columns})"
 
 
+# accepted ``how`` spellings -> canonical join type
+_JOIN_TYPE_ALIASES = {
+    "inner": "inner",
+    "left": "left_outer", "left_outer": "left_outer",
+    "leftouter": "left_outer",
+    "right": "right_outer", "right_outer": "right_outer",
+    "rightouter": "right_outer",
+    "full": "full_outer", "outer": "full_outer",
+    "full_outer": "full_outer", "fullouter": "full_outer",
+    "semi": "left_semi", "left_semi": "left_semi", "leftsemi": "left_semi",
+    "anti": "left_anti", "left_anti": "left_anti", "leftanti": "left_anti",
+}
+
+
+def canonical_join_type(join_type: str) -> str:
+    """Canonical name (``inner``, ``left_outer``, ``right_outer``,
+    ``full_outer``, ``left_semi``, ``left_anti``) for a ``how`` spelling."""
+    key = join_type.strip().lower() if isinstance(join_type, str) else None
+    if key not in _JOIN_TYPE_ALIASES:
+        raise HyperspaceException(
+            f"Unsupported join type {join_type!r}; expected one of "
+            f"{sorted(_JOIN_TYPE_ALIASES)}")
+    return _JOIN_TYPE_ALIASES[key]
+
+
 class Join(LogicalPlan):
     def __init__(self, left: LogicalPlan, right: LogicalPlan,
                  condition: Expr, join_type: str = "inner"):
         super().__init__([left, right])
-        if join_type != "inner":
-            raise HyperspaceException("Only inner joins supported in v0")
         self.condition = condition
-        self.join_type = join_type
+        self.join_type = canonical_join_type(join_type)
 
     @property
     def left(self):
@@ -145,13 +168,18 @@ class Join(LogicalPlan):
         return self.children[1]
 
     def output_columns(self):
+        if self.join_type in ("left_semi", "left_anti"):
+            return self.left.output_columns()
         return self.left.output_columns() + self.right.output_columns()
 
     def with_children(self, children):
         return Join(children[0], children[1], self.condition, self.join_type)
 
     def _node_str(self):
-        return f"Join({self.condition!r})"
+        # inner keeps its historical rendering (plan-stability goldens)
+        if self.join_type == "inner":
+            return f"Join({self.condition!r})"
+        return f"Join({self.join_type}, {self.condition!r})"
 
 
 class IndexScan(LogicalPlan):
