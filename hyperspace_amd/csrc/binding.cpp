@@ -43,6 +43,10 @@ torch::Tensor murmur3_bucket(std::vector<torch::Tensor> keys,
   TORCH_CHECK(!keys.empty(), "need at least one key column");
   TORCH_CHECK(masks.empty() || masks.size() == keys.size(),
               "masks must be empty or parallel to keys");
+  // pmod by zero is undefined in the kernel
+  TORCH_CHECK(num_buckets > 0 && num_buckets <= (int64_t)INT32_MAX,
+              "murmur3_bucket: num_buckets must be in 1..INT32_MAX, got ",
+              num_buckets);
   auto n = keys[0].numel();
   auto dev = keys[0].device();
   auto h = torch::empty({n}, torch::dtype(torch::kInt32).device(dev));
@@ -156,6 +160,30 @@ std::tuple<torch::Tensor, torch::Tensor> radix_sort_pairs(
   return {out_keys, out_payload};
 }
 
+// The pass plan the sort runs for a varying-bit mask: (radix, shifts).
+// Thin wrapper over the planner both payload widths call, so a test can
+// see which digit width a process runs (HS_RS_9BIT is read once).
+std::tuple<int64_t, std::vector<int64_t>> radix_sort_plan(uint64_t mask) {
+  int shifts[8];
+  int npass = 0;
+  int radix = hsk::radix_sort_plan(mask, shifts, &npass);
+  return {(int64_t)radix, std::vector<int64_t>(shifts, shifts + npass)};
+}
+
+// Device-wide exclusive scan of an int64 tensor: (out, total), total a
+// 1-element device tensor.
+std::tuple<torch::Tensor, torch::Tensor> exclusive_scan(torch::Tensor t) {
+  check_cuda(t, "t");
+  TORCH_CHECK(t.scalar_type() == torch::kInt64, "t must be int64");
+  auto out = torch::empty_like(t);
+  auto total = torch::empty(
+      {1}, torch::dtype(torch::kInt64).device(t.device()));
+  hsk::exclusive_scan_i64(t.data_ptr<int64_t>(), out.data_ptr<int64_t>(),
+                          t.numel(), total.data_ptr<int64_t>(),
+                          current_stream());
+  return {out, total};
+}
+
 // mode: hsk::MergeJoinMode (0 inner, 1 left outer, 2 left semi, 3 left
 // anti).  Semi and anti return an empty second tensor.
 std::tuple<torch::Tensor, torch::Tensor> merge_join(torch::Tensor lkeys,
@@ -249,8 +277,16 @@ std::tuple<torch::Tensor, torch::Tensor> segmented_minmax(
   return {mins, maxs};
 }
 
+// the kernels take pos % m_bits: m_bits == 0 is undefined
+void check_bloom_args(int64_t m_bits, int64_t k) {
+  TORCH_CHECK(m_bits > 0 && k >= 0 && k <= (int64_t)INT32_MAX,
+              "bloom: need m_bits > 0 and k >= 0, got m_bits=", m_bits,
+              " k=", k);
+}
+
 torch::Tensor bloom_build(torch::Tensor vals, int64_t m_bits, int64_t k) {
   check_cuda(vals, "vals");
+  check_bloom_args(m_bits, k);
   int64_t words = (m_bits + 63) / 64;
   auto out = torch::zeros(
       {words}, torch::dtype(torch::kInt64).device(vals.device()));
@@ -263,6 +299,7 @@ torch::Tensor bloom_build(torch::Tensor vals, int64_t m_bits, int64_t k) {
 torch::Tensor bloom_probe(torch::Tensor vals, torch::Tensor words,
                           int64_t m_bits, int64_t k) {
   check_cuda(vals, "vals");
+  check_bloom_args(m_bits, k);
   auto words_d = words.to(vals.device(), torch::kInt64).contiguous();
   auto out = torch::empty(
       {vals.numel()}, torch::dtype(torch::kBool).device(vals.device()));
@@ -275,6 +312,7 @@ torch::Tensor bloom_probe(torch::Tensor vals, torch::Tensor words,
 torch::Tensor bloom_probe_many(torch::Tensor vals, torch::Tensor words,
                                int64_t m_bits, int64_t k) {
   check_cuda(vals, "vals");
+  check_bloom_args(m_bits, k);
   TORCH_CHECK(words.dim() == 2, "words must be [n_filters, words]");
   auto words_d = words.to(vals.device(), torch::kInt64).contiguous();
   int64_t n_filters = words_d.size(0);
@@ -290,6 +328,11 @@ torch::Tensor bloom_probe_many(torch::Tensor vals, torch::Tensor words,
 torch::Tensor zorder_key(std::vector<torch::Tensor> cols,
                          int64_t bits_per_col) {
   TORCH_CHECK(!cols.empty() && cols.size() <= 8, "1..8 zorder columns");
+  // the kernel shifts by 63 - (b * n_cols + c): past 64 bits is undefined
+  TORCH_CHECK(bits_per_col >= 0 &&
+                  (int64_t)cols.size() * bits_per_col <= 64,
+              "zorder_key: need bits_per_col >= 0 and n_cols * "
+              "bits_per_col <= 64, got ", cols.size(), " x ", bits_per_col);
   auto n = cols[0].numel();
   std::vector<const uint64_t*> ptrs;
   for (auto& c : cols) {
@@ -596,6 +639,9 @@ torch::Tensor rle_decode(torch::Tensor src_u8_dev, torch::Tensor kind,
                          torch::Tensor bitoff, torch::Tensor value,
                          int64_t bit_width, int64_t n_out) {
   check_cuda(src_u8_dev, "src");
+  // values are extracted from a 5-byte window into u32 outputs
+  TORCH_CHECK(bit_width >= 0 && bit_width <= 32,
+              "rle_decode: bit_width must be in 0..32, got ", bit_width);
   auto dev = src_u8_dev.device();
   auto k = kind.to(dev), o = out_off.to(dev), l = len.to(dev),
        b = bitoff.to(dev), v = value.to(dev);
@@ -673,6 +719,11 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("masks") = std::vector<torch::Tensor>{});
   m.def("normalize_key", &normalize_key, "order-preserving u64 key");
   m.def("radix_sort_pairs", &radix_sort_pairs, "stable LSD radix sort");
+  m.def("radix_sort_plan", &radix_sort_plan,
+        "pass plan of the radix sort for a varying-bit mask: "
+        "(radix, [shifts])");
+  m.def("exclusive_scan", &exclusive_scan,
+        "device-wide exclusive scan of an int64 tensor: (out, total)");
   m.def("merge_join", &merge_join, "segmented sorted merge join",
         py::arg("lkeys"), py::arg("rkeys"), py::arg("lseg"), py::arg("rseg"),
         py::arg("mode") = 0);

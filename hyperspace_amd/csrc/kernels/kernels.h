@@ -33,6 +33,10 @@ void radix_sort_pairs32(uint64_t* keys, int32_t* payload,
                         hipStream_t stream);
 // histogram buffer size requirement (u32 elements)
 int64_t radix_sort_hist_size(int64_t n);
+// pass plan the sort runs for a varying-bit mask (OR of key ^ key[0]):
+// returns the radix (256, or 512 when HS_RS_9BIT=1 and 9-bit digits save
+// a pass) and fills shifts[0..*npass) with the digit shifts, ascending.
+int radix_sort_plan(uint64_t mask, int shifts[8], int* npass);
 
 // K4: segmented sorted merge join, two-phase per-tile form.  Phase 1
 // writes one pair-count per 256-row left tile; after an exclusive scan

@@ -474,6 +474,38 @@ __global__ void k_rs_scatter(const uint64_t* __restrict__ keys,
   }
 }
 
+// Pass planning, shared by both payload instantiations (and by the
+// binding's radix_sort_plan, so tests see exactly what the sort runs):
+// byte-aligned digits with constant-byte skipping vs 9-bit digits
+// anchored at the lowest varying bit — take whichever needs fewer passes
+// (26-bit bench keys: 4 byte passes -> 3 nine-bit passes).  Both cover
+// every varying bit exactly once in LSB->MSB order, so LSD stability is
+// preserved.  Returns the radix (256 or 512); shifts[0..*npass) are the
+// digit shifts in pass order.
+int radix_sort_plan(uint64_t mask, int shifts[8], int* npass) {
+  int shifts8[8], n8 = 0;
+  for (int s = 0; s < 64; s += 8)
+    if ((mask >> s) & 255ull) shifts8[n8++] = s;
+  int shifts9[8], n9 = 0;
+  if (mask) {
+    for (int s = __builtin_ctzll(mask); s < 64; s += 9)
+      if ((mask >> s) & 511ull) shifts9[n9++] = s;
+  }
+  // 9-bit passes saved one pass for 26-bit keys but measured ~10%
+  // slower end-to-end on MI355X (the scatter is wave-cap bound, and the
+  // wider digit costs an extra ballot + 2-digit scan per thread) —
+  // byte passes stay the default; HS_RS_9BIT=1 re-enables the wide
+  // planner for future tuning (profiles/r2_summary.md).
+  static const bool want9 = [] {
+    const char* e = getenv("HS_RS_9BIT");
+    return e && e[0] == '1';
+  }();
+  bool use9 = n9 < n8 && want9;
+  *npass = use9 ? n9 : n8;
+  for (int i = 0; i < *npass; i++) shifts[i] = use9 ? shifts9[i] : shifts8[i];
+  return use9 ? 512 : 256;
+}
+
 template <typename P>
 static void radix_sort_impl(uint64_t* keys, P* payload, uint64_t* tmp_keys,
                             P* tmp_payload, uint32_t* hist,
@@ -498,32 +530,10 @@ static void radix_sort_impl(uint64_t* keys, P* payload, uint64_t* tmp_keys,
   uint64_t* kb = tmp_keys;
   P* pa = payload;
   P* pb = tmp_payload;
-  // pass planning: byte-aligned digits with constant-byte skipping vs
-  // 9-bit digits anchored at the lowest varying bit — take whichever
-  // needs fewer passes (26-bit bench keys: 4 byte passes -> 3 nine-bit
-  // passes).  Both cover every varying bit exactly once in LSB->MSB
-  // order, so LSD stability is preserved.
-  int shifts8[8], n8 = 0;
-  for (int s = 0; s < 64; s += 8)
-    if ((mask >> s) & 255ull) shifts8[n8++] = s;
-  int shifts9[8], n9 = 0;
-  if (mask) {
-    for (int s = __builtin_ctzll(mask); s < 64; s += 9)
-      if ((mask >> s) & 511ull) shifts9[n9++] = s;
-  }
-  // 9-bit passes saved one pass for 26-bit keys but measured ~10%
-  // slower end-to-end on MI355X (the scatter is wave-cap bound, and the
-  // wider digit costs an extra ballot + 2-digit scan per thread) —
-  // byte passes stay the default; HS_RS_9BIT=1 re-enables the wide
-  // planner for future tuning (profiles/r2_summary.md).
-  static const bool want9 = [] {
-    const char* e = getenv("HS_RS_9BIT");
-    return e && e[0] == '1';
-  }();
-  bool use9 = n9 < n8 && want9;
-  const int* shifts = use9 ? shifts9 : shifts8;
-  int npass = use9 ? n9 : n8;
-  int radix = use9 ? 512 : 256;
+  int shifts[8];
+  int npass = 0;
+  int radix = radix_sort_plan(mask, shifts, &npass);
+  bool use9 = radix == 512;
   for (int pi = 0; pi < npass; pi++) {
     int shift = shifts[pi];
     HIP_CHECK(hipMemsetAsync(hist, 0,

@@ -92,13 +92,17 @@ def test_radix_sort_small_range_pass_skipping():
 
 
 @pytest.mark.parametrize("lo,hi", [
-    (0, 1 << 26),            # bench shape: 26 bits -> three 9-bit passes
-    (1 << 8, 1 << 17),       # bits 8..16 -> one 9-bit pass
-    (0, 1 << 18),            # 18 bits -> two 9-bit passes
+    (0, 1 << 26),            # bench shape: 4 byte passes (three 9-bit)
+    (1 << 8, 1 << 17),       # bits 8..16: 2 byte passes (one 9-bit)
+    (0, 1 << 18),            # 18 bits: 3 byte passes (two 9-bit)
 ])
 def test_radix_sort_nine_bit_planner(lo, hi):
-    """Key shapes where the 9-bit pass planner beats byte passes must
-    still sort stably and bit-identically to the CPU oracle."""
+    """Key shapes where a 9-bit pass planner would beat byte passes must
+    sort stably and bit-identically to the CPU oracle.  In the default
+    environment this exercises BYTE passes: the 9-bit digit needs
+    HS_RS_9BIT=1 at process start, which
+    test_kernel_edges_gpu.py::test_radix_sort_512_bin_path provides in a
+    child process."""
     rng = np.random.default_rng(lo % 13 + hi % 7)
     keys = cpu_ref.normalize_key(torch.from_numpy(
         rng.integers(lo, hi, 2_000_000, dtype=np.int64)))
