@@ -23,7 +23,7 @@ from __future__ import annotations
 
 import os
 import struct
-from typing import Any, Dict, List, Optional, Tuple
+from typing import Any, Dict, List, NamedTuple, Optional, Tuple
 
 import numpy as np
 
@@ -396,10 +396,11 @@ def write_parquet_native(columns: "Dict[str, np.ndarray]", path: str,
                              mask is not None, dict_off))
             layouts.append(ColumnChunkLayout(
                 name, np.dtype("int32"),
-                [("dict", offset + len(header) + lvl_len + 1,
-                  offset + len(header) + len(payload), num_rows, bw)],
+                [Page("dict", offset + len(header) + lvl_len + 1,
+                      offset + len(header) + len(payload), num_rows, bw)],
                 num_rows, "dict",
-                (dict_off + len(dict_header), len(arr.values)), [mask],
+                DictPage(dict_off + len(dict_header), offset,
+                         len(arr.values)), [mask],
                 is_string=True, str_values=list(arr.values)))
             chunks.append(header)
             chunks.append(payload)
@@ -426,7 +427,8 @@ def write_parquet_native(columns: "Dict[str, np.ndarray]", path: str,
                          null_count, mask is not None, None))
         layouts.append(ColumnChunkLayout(
             name, arr.dtype,
-            [("plain", offset + len(header) + lvl_len, num_rows)],
+            [Page("plain", offset + len(header) + lvl_len,
+                  offset + len(header) + nbytes, num_rows)],
             num_rows, "plain", None, [mask]))
         chunks.append(header)
         chunks.append(payload)
@@ -515,13 +517,50 @@ def write_parquet_native(columns: "Dict[str, np.ndarray]", path: str,
 # Reader (page layout for the device decode path)
 # ---------------------------------------------------------------------------
 
-class ColumnChunkLayout:
-    """Per-column page layout.
+class Page(NamedTuple):
+    """One data page of a column chunk.  ``start``/``end`` bound the bytes
+    the decoder reads in the file and ``num_values`` counts ROWS (nulls
+    included), for every kind:
 
-    encoding "plain": pages = [("plain", values byte offset, num values)]
-    encoding "dict":  pages = [("dict", payload start, payload end,
-                      num values, bit width), ...] of RLE/bit-packed index
-                      payloads, plus dict_page = (values offset, dict size)
+    "plain"    uncompressed PLAIN numeric values (compacted, non-null)
+    "dict"     uncompressed RLE/bit-packed dictionary indices; ``start``
+               is past the bit-width byte, which is in ``bit_width``
+    "splain"   uncompressed PLAIN byte-array (string) values
+    "plain_z" / "dict_z" / "splain_z"
+               the same payloads under a codec: ``start``/``end`` bound
+               the compressed bytes and ``unc_size`` is their decompressed
+               size; ``has_levels`` says the decompressed payload opens
+               with a 4-byte-length-prefixed def-level block (DataPage
+               V1); ``is_compressed`` is False only for a DataPageV2 page
+               stored uncompressed inside a compressed chunk.
+    """
+    kind: str
+    start: int
+    end: int
+    num_values: int
+    bit_width: int = 0
+    unc_size: int = 0
+    has_levels: bool = False
+    is_compressed: bool = True
+
+
+class DictPage(NamedTuple):
+    """A chunk's PLAIN dictionary page payload: ``num_values`` entries in
+    file bytes [start, end); under a codec those bytes are compressed
+    and decompress to ``unc_size``."""
+    start: int
+    end: int
+    num_values: int
+    unc_size: int = 0
+    compressed: bool = False
+
+
+class ColumnChunkLayout:
+    """Per-column-chunk page layout: ``pages`` is a list of Page,
+    ``dict_page`` a DictPage or None, and ``encoding`` names the chunk by
+    its most demanding page kind ("dict" > "splain" > "dict_z" >
+    "splain_z" > "plain_z" > "plain"); a dictionary chunk can end in
+    PLAIN pages (the writer's mid-chunk dictionary overflow).
 
     ``page_masks`` parallels ``pages``: a bool validity array per page for
     OPTIONAL columns with nulls in that page, else None.  A page's stored
@@ -555,10 +594,9 @@ class ColumnChunkLayout:
         """The string dictionary: cached from the writer, else parsed
         from the PLAIN dictionary page payload in ``data``."""
         if self.str_values is None:
-            off, n = self.dict_page
             vals = []
-            pos = off
-            for _ in range(n):
+            pos = self.dict_page.start
+            for _ in range(self.dict_page.num_values):
                 ln = struct.unpack_from("<I", data, pos)[0]
                 pos += 4
                 vals.append(bytes(data[pos:pos + ln]).decode("utf-8"))
@@ -680,249 +718,235 @@ def read_native_layout(path: str,
 def _walk_row_group(rg, pf_schema, data, want
                     ) -> Optional[List[ColumnChunkLayout]]:
     out: List[ColumnChunkLayout] = []
-    col_index = -1
     for i in range(rg.num_columns):
         col = rg.column(i)
-        col_index += 1
-        name = col.path_in_schema
-        if want is not None and name.lower() not in want:
+        if want is not None and col.path_in_schema.lower() not in want:
             continue
-        codec = col.compression.upper()
-        # SNAPPY decodes on device (or host for copy-dense pages);
-        # GZIP/ZSTD/BROTLI/LZ4 pages decode on host codec threads but
-        # keep the native page-assembly path (no pyarrow table
-        # fallback).  Parquet "LZ4"/"LZ4_RAW" pages are raw LZ4 blocks
-        # (arrow writes block format for both) -> pa.Codec("lz4_raw").
-        if codec not in ("UNCOMPRESSED", "SNAPPY", "GZIP", "ZSTD",
-                         "BROTLI", "LZ4", "LZ4_RAW"):
+        lay = _walk_chunk(col, pf_schema.column(i), data)
+        if lay is None:
             return None
-        encs = set(col.encodings)
-        is_dict = bool(encs & {"PLAIN_DICTIONARY", "RLE_DICTIONARY"})
-        if encs - {"PLAIN", "RLE", "BIT_PACKED", "PLAIN_DICTIONARY",
-                   "RLE_DICTIONARY"}:
-            return None
-        is_string = False
-        if col.physical_type == "BYTE_ARRAY":
-            # dictionary-encoded strings decode natively (codes + one
-            # dictionary parse), uncompressed or compressed; PLAIN
-            # byte-array pages parse host-side into codes ("splain" /
-            # "splain_z" after decompression)
-            is_string = True
-            np_dtype = np.dtype("int32")
-        else:
-            ptype = {"INT64": T_INT64, "INT32": T_INT32, "FLOAT": T_FLOAT,
-                     "DOUBLE": T_DOUBLE}.get(col.physical_type)
-            if ptype is None:
-                return None
-            np_dtype = _PARQUET_TO_NP[ptype]
-        # OPTIONAL columns carry a def-level prefix per page; when the
-        # chunk statistics prove null_count == 0 the levels are skipped
-        # without decoding, else each page's levels become a validity
-        # mask.  Nested leaves (max_def > 1 or repeated) use wider level
-        # encodings: pyarrow fallback.
-        col_schema = pf_schema.column(col_index)
-        if col_schema.max_repetition_level > 0:
-            return None  # repeated (list) leaves: pyarrow
-        max_def = col_schema.max_definition_level
-        has_levels = max_def > 0
-        st = col.statistics
-        chunk_all_valid = st is not None and st.null_count == 0
-
-        dict_page = None
-        pos = col.data_page_offset
-        if is_dict:
-            dict_off = col.dictionary_page_offset
-            if dict_off is None:
-                return None
-            r = TReader(data, dict_off)
-            try:
-                hdr = r.read_struct()
-            except Exception:  # noqa: BLE001
-                return None
-            if hdr.get(1) != 2:  # DICTIONARY_PAGE
-                return None
-            dict_n = hdr.get(7, {}).get(1)
-            if dict_n is None:
-                return None
-            if codec != "UNCOMPRESSED":
-                if hdr.get(2) is None:
-                    return None
-                dict_page = ("z", r.pos, r.pos + hdr.get(3), dict_n,
-                             hdr.get(2))
-            else:
-                dict_page = (r.pos, dict_n)
-            if dict_off >= pos:
-                # dictionary physically precedes data pages
-                pos = r.pos + hdr.get(3)
-
-        seen = 0
-        pages: List[Tuple] = []
-        page_masks: List[Optional[np.ndarray]] = []
-        while seen < col.num_values:
-            r = TReader(data, pos)
-            try:
-                hdr = r.read_struct()
-            except Exception:  # noqa: BLE001
-                return None
-            page_bytes = hdr.get(3)
-            if hdr.get(1) == 2:  # stray dictionary page: skip
-                pos = r.pos + page_bytes
-                continue
-            if hdr.get(1) == 3:  # DataPageV2
-                # levels are stored UNCOMPRESSED at the payload start
-                # with a KNOWN byte length (no 4-byte prefix); only the
-                # data section after them is subject to the codec
-                # (parquet-format PageHeader.data_page_header_v2)
-                d2 = hdr.get(8, {})
-                num_values = d2.get(1)
-                dl_len = d2.get(5, 0) or 0
-                rl_len = d2.get(6, 0) or 0
-                if num_values is None or rl_len:
-                    return None  # repeated leaves: pyarrow
-                enc2 = d2.get(4)
-                is_comp = codec != "UNCOMPRESSED" and \
-                    d2.get(7, True) is not False
-                values_off = r.pos
-                page_end = r.pos + page_bytes
-                mask = None
-                if dl_len:
-                    if not chunk_all_valid:
-                        mask = _decode_defs(data, values_off, dl_len,
-                                            num_values, max_def)
-                    values_off += dl_len
-                n_valid = int(mask.sum()) if mask is not None \
-                    else num_values
-                if codec != "UNCOMPRESSED":
-                    # under a codec, every V2 page becomes a z page so
-                    # the chunk stays uniform (the dictionary page is
-                    # always compressed); per-page is_compressed=false
-                    # pages carry is_comp=False (7th element) and are
-                    # identity-copied into scratch at decode
-                    if is_comp:
-                        unc = hdr.get(2)
-                        if unc is None:
-                            return None
-                        unc_data = unc - dl_len - rl_len
-                    else:
-                        unc_data = page_end - values_off
-                    if is_dict and enc2 in (2, 8):
-                        pages.append(("dict_z", values_off, page_end,
-                                      num_values, unc_data, False,
-                                      is_comp))
-                    elif enc2 == ENC_PLAIN:
-                        pages.append((
-                            "splain_z" if is_string else "plain_z",
-                            values_off, page_end, num_values, unc_data,
-                            False, is_comp))
-                    else:
-                        return None
-                else:
-                    if is_dict and enc2 in (2, 8):
-                        bit_width = data[values_off]
-                        pages.append(("dict", values_off + 1, page_end,
-                                      num_values, bit_width))
-                    elif is_string and enc2 == ENC_PLAIN:
-                        pages.append(("splain", values_off, page_end,
-                                      num_values))
-                    elif enc2 == ENC_PLAIN:
-                        expected = n_valid * np_dtype.itemsize
-                        if values_off + expected > page_end:
-                            return None
-                        pages.append(("plain", values_off, num_values))
-                    else:
-                        return None
-                page_masks.append(mask)
-                seen += num_values
-                pos = page_end
-                continue
-            if hdr.get(1) != PAGE_DATA:
-                return None
-            dph = hdr.get(5, {})
-            num_values = dph.get(1)
-            if num_values is None:
-                return None
-            values_off = r.pos
-            page_end = r.pos + page_bytes
-            mask = None
-            if codec != "UNCOMPRESSED":
-                # compressed page: record the compressed extent +
-                # uncompressed size; the device decompresses, then (for
-                # OPTIONAL all-valid chunks) the level prefix is skipped
-                # post-decompression.  Dictionary-index pages D2H their
-                # small decompressed payload for the host run parser.
-                unc = hdr.get(2)
-                if unc is None:
-                    return None
-                pe = dph.get(2)
-                if is_dict and pe in (2, 8):
-                    pages.append(("dict_z", values_off, page_end,
-                                  num_values, unc, has_levels))
-                elif pe == ENC_PLAIN:
-                    # compressed PLAIN byte-array pages (whole-chunk
-                    # PLAIN strings, or a mid-chunk dictionary
-                    # overflow) decompress like any page, then the
-                    # payload D2Hs for the host byte-array parse
-                    kind = "splain_z" if is_string else "plain_z"
-                    pages.append((kind, values_off, page_end,
-                                  num_values, unc, has_levels))
-                else:
-                    return None
-                page_masks.append(None)
-                seen += num_values
-                pos = page_end
-                continue
-            if has_levels:
-                lvl_len = struct.unpack_from("<I", data, values_off)[0]
-                if not chunk_all_valid:
-                    mask = _decode_defs(data, values_off + 4, lvl_len,
-                                        num_values, max_def)
-                values_off += 4 + lvl_len
-            n_valid = int(mask.sum()) if mask is not None else num_values
-            page_enc = dph.get(2)
-            if is_dict and page_enc in (2, 8):  # PLAIN_DICT / RLE_DICT
-                bit_width = data[values_off]
-                pages.append(("dict", values_off + 1, page_end,
-                              num_values, bit_width))
-            elif is_string and page_enc == ENC_PLAIN:
-                # PLAIN byte-array page: a whole-chunk PLAIN string
-                # column, or pyarrow's mid-chunk dictionary overflow.
-                # The (compacted) length-prefixed values parse on host
-                # (parse_byte_arrays) and dictionary-encode per chunk.
-                pages.append(("splain", values_off, page_end,
-                              num_values))
-            elif is_string:
-                return None
-            elif page_enc == ENC_PLAIN:
-                # also reached as the writer's mid-chunk fallback when a
-                # dictionary overflows: later pages switch to PLAIN
-                expected = n_valid * np_dtype.itemsize
-                if values_off + expected > page_end:
-                    return None
-                pages.append(("plain", values_off, num_values))
-            else:
-                return None
-            page_masks.append(mask)
-            seen += num_values
-            pos = page_end
-        if seen != col.num_values:
-            return None
-        if any(pg[0] == "dict" for pg in pages):
-            enc_kind = "dict"
-        elif any(pg[0] == "splain" for pg in pages):
-            enc_kind = "splain"
-        elif any(pg[0] == "dict_z" for pg in pages):
-            enc_kind = "dict_z"
-        elif any(pg[0] == "splain_z" for pg in pages):
-            enc_kind = "splain_z"
-        elif any(pg[0] == "plain_z" for pg in pages):
-            enc_kind = "plain_z"
-        else:
-            enc_kind = "plain"
-        out.append(ColumnChunkLayout(name, np_dtype, pages,
-                                     col.num_values, enc_kind, dict_page,
-                                     page_masks, is_string=is_string,
-                                     codec=codec, max_def=max_def))
+        out.append(lay)
     return out
+
+
+class _ChunkInfo(NamedTuple):
+    """What the page walkers need to know about their column chunk."""
+    codec: str
+    is_dict: bool
+    is_string: bool
+    np_dtype: Any
+    max_def: int
+    all_valid: bool  # statistics prove null_count == 0
+
+
+def _chunk_info(col, col_schema) -> Optional[_ChunkInfo]:
+    codec = col.compression.upper()
+    # SNAPPY decodes on device (or host for copy-dense pages);
+    # GZIP/ZSTD/BROTLI/LZ4 pages decode on host codec threads but keep
+    # the native page-assembly path (no pyarrow table fallback).  Parquet
+    # "LZ4"/"LZ4_RAW" pages are raw LZ4 blocks (arrow writes block format
+    # for both) -> pa.Codec("lz4_raw").
+    if codec not in ("UNCOMPRESSED", "SNAPPY", "GZIP", "ZSTD", "BROTLI",
+                     "LZ4", "LZ4_RAW"):
+        return None
+    encs = set(col.encodings)
+    if encs - {"PLAIN", "RLE", "BIT_PACKED", "PLAIN_DICTIONARY",
+               "RLE_DICTIONARY"}:
+        return None
+    is_string = col.physical_type == "BYTE_ARRAY"
+    if is_string:
+        # dictionary-encoded strings decode natively (codes + one
+        # dictionary parse), uncompressed or compressed; PLAIN byte-array
+        # pages parse host-side into codes ("splain" / "splain_z" after
+        # decompression)
+        np_dtype = np.dtype("int32")
+    else:
+        ptype = {"INT64": T_INT64, "INT32": T_INT32, "FLOAT": T_FLOAT,
+                 "DOUBLE": T_DOUBLE}.get(col.physical_type)
+        if ptype is None:
+            return None
+        np_dtype = _PARQUET_TO_NP[ptype]
+    # OPTIONAL columns carry a def-level prefix per page; when the chunk
+    # statistics prove null_count == 0 the levels are skipped without
+    # decoding, else each page's levels become a validity mask.  Repeated
+    # (list) leaves: pyarrow fallback.
+    if col_schema.max_repetition_level > 0:
+        return None
+    st = col.statistics
+    return _ChunkInfo(
+        codec, bool(encs & {"PLAIN_DICTIONARY", "RLE_DICTIONARY"}),
+        is_string, np_dtype, col_schema.max_definition_level,
+        st is not None and st.null_count == 0)
+
+
+def _walk_chunk(col, col_schema, data) -> Optional[ColumnChunkLayout]:
+    ci = _chunk_info(col, col_schema)
+    if ci is None:
+        return None
+    dict_page = None
+    pos = col.data_page_offset
+    if ci.is_dict:
+        dict_off = col.dictionary_page_offset
+        if dict_off is None:
+            return None
+        r = TReader(data, dict_off)
+        try:
+            hdr = r.read_struct()
+        except Exception:  # noqa: BLE001
+            return None
+        start = r.pos
+        dict_n = hdr.get(7, {}).get(1)
+        if hdr.get(1) != 2 or dict_n is None:  # not a DICTIONARY_PAGE
+            return None
+        if ci.codec != "UNCOMPRESSED":
+            if hdr.get(2) is None:
+                return None
+            dict_page = DictPage(start, start + hdr.get(3), dict_n,
+                                 hdr.get(2), True)
+        else:
+            dict_page = DictPage(start, start + hdr.get(3), dict_n)
+        if dict_off >= pos:
+            # dictionary physically precedes data pages
+            pos = start + hdr.get(3)
+
+    seen = 0
+    pages: List[Page] = []
+    page_masks: List[Optional[np.ndarray]] = []
+    chunk_values = col.num_values
+    while seen < chunk_values:  # the GIL-bound hot loop of a cold read
+        r = TReader(data, pos)
+        try:
+            hdr = r.read_struct()
+        except Exception:  # noqa: BLE001
+            return None
+        start = r.pos
+        pos = start + hdr.get(3)
+        page_type = hdr.get(1)
+        if page_type == PAGE_DATA:
+            got = _data_page_v1(ci, hdr, data, start)
+        elif page_type == 3:
+            got = _data_page_v2(ci, hdr, data, start)
+        elif page_type == 2:  # stray dictionary page: skip
+            continue
+        else:
+            return None
+        if got is None:
+            return None
+        page, mask = got
+        pages.append(page)
+        page_masks.append(mask)
+        seen += page.num_values
+    if seen != chunk_values:
+        return None
+    kinds = {pg.kind for pg in pages}
+    enc_kind = next((k for k in ("dict", "splain", "dict_z", "splain_z",
+                                 "plain_z") if k in kinds), "plain")
+    return ColumnChunkLayout(col.path_in_schema, ci.np_dtype, pages,
+                             chunk_values, enc_kind, dict_page,
+                             page_masks, is_string=ci.is_string,
+                             codec=ci.codec, max_def=ci.max_def)
+
+
+def _raw_page(ci: _ChunkInfo, enc, data, start, end, num_values, mask
+              ) -> Optional[Page]:
+    """Uncompressed data page whose values begin at ``start``."""
+    if ci.is_dict and enc in (2, 8):  # PLAIN_DICT / RLE_DICT
+        return Page("dict", start + 1, end, num_values, data[start])
+    if enc != ENC_PLAIN:
+        return None
+    if ci.is_string:
+        # PLAIN byte-array page: a whole-chunk PLAIN string column, or
+        # pyarrow's mid-chunk dictionary overflow.  The (compacted)
+        # length-prefixed values parse on host (parse_byte_arrays) and
+        # dictionary-encode per chunk.
+        return Page("splain", start, end, num_values)
+    # also reached as the writer's mid-chunk fallback when a dictionary
+    # overflows: later pages switch to PLAIN
+    n_valid = int(mask.sum()) if mask is not None else num_values
+    if start + n_valid * ci.np_dtype.itemsize > end:
+        return None
+    return Page("plain", start, end, num_values)
+
+
+def _z_page(ci: _ChunkInfo, enc, start, end, num_values, unc, has_levels,
+            is_compressed=True) -> Optional[Page]:
+    """Data page under a codec: record the compressed extent + the
+    uncompressed size; the read decompresses, then skips or decodes the
+    level prefix.  PLAIN byte-array pages (whole-chunk PLAIN strings, or
+    a mid-chunk dictionary overflow) decompress like any page, then the
+    payload parses on host."""
+    if ci.is_dict and enc in (2, 8):
+        kind = "dict_z"
+    elif enc == ENC_PLAIN:
+        kind = "splain_z" if ci.is_string else "plain_z"
+    else:
+        return None
+    return Page(kind, start, end, num_values, 0, unc, has_levels,
+                is_compressed)
+
+
+def _data_page_v1(ci: _ChunkInfo, hdr, data, values_off):
+    """-> (Page, validity mask or None), or None to decline the file."""
+    dph = hdr.get(5, {})
+    num_values = dph.get(1)
+    if num_values is None:
+        return None
+    page_end = values_off + hdr.get(3)
+    mask = None
+    if ci.codec != "UNCOMPRESSED":
+        if hdr.get(2) is None:
+            return None
+        page = _z_page(ci, dph.get(2), values_off, page_end, num_values,
+                       hdr.get(2), ci.max_def > 0)
+    else:
+        if ci.max_def > 0:
+            lvl_len = struct.unpack_from("<I", data, values_off)[0]
+            if not ci.all_valid:
+                mask = _decode_defs(data, values_off + 4, lvl_len,
+                                    num_values, ci.max_def)
+            values_off += 4 + lvl_len
+        page = _raw_page(ci, dph.get(2), data, values_off, page_end,
+                         num_values, mask)
+    return None if page is None else (page, mask)
+
+
+def _data_page_v2(ci: _ChunkInfo, hdr, data, values_off):
+    """DataPageV2: levels are stored UNCOMPRESSED at the payload start
+    with a KNOWN byte length (no 4-byte prefix); only the data section
+    after them is subject to the codec (parquet-format
+    PageHeader.data_page_header_v2).
+    -> (Page, validity mask or None), or None to decline the file."""
+    d2 = hdr.get(8, {})
+    num_values = d2.get(1)
+    dl_len = d2.get(5, 0) or 0
+    rl_len = d2.get(6, 0) or 0
+    if num_values is None or rl_len:
+        return None  # repeated leaves: pyarrow
+    page_end = values_off + hdr.get(3)
+    mask = None
+    if dl_len:
+        if not ci.all_valid:
+            mask = _decode_defs(data, values_off, dl_len, num_values,
+                                ci.max_def)
+        values_off += dl_len
+    if ci.codec == "UNCOMPRESSED":
+        page = _raw_page(ci, d2.get(4), data, values_off, page_end,
+                         num_values, mask)
+    else:
+        # under a codec, every V2 page becomes a z page so the chunk
+        # stays uniform (the dictionary page is always compressed);
+        # per-page is_compressed=false pages are identity-copied into
+        # scratch at decode
+        is_comp = d2.get(7, True) is not False
+        if not is_comp:
+            unc_data = page_end - values_off
+        elif hdr.get(2) is None:
+            return None
+        else:
+            unc_data = hdr.get(2) - dl_len - rl_len
+        page = _z_page(ci, d2.get(4), values_off, page_end, num_values,
+                       unc_data, False, is_comp)
+    return None if page is None else (page, mask)
 
 
 def _decode_rle_indices(data, off: int, end: int, n: int, bw: int
@@ -1022,6 +1046,31 @@ def decode_splain_pages(buf, starts: List[int], ends: List[int],
     return np.ascontiguousarray(codes), list(vals)
 
 
+def merge_string_dicts(dicts: List[List[str]]) -> Tuple[List[str], bool]:
+    """One dictionary for a string column read in pieces ->
+    (merged values, needs_remap).  Parquet dictionaries are in INSERTION
+    order and StringColumn requires SORTED values (code order = lex
+    order): identical, sorted dictionaries keep the first one as is;
+    anything else becomes the sorted union and every piece's codes go
+    through its string_remap_tables entry."""
+    if not dicts:
+        return [], False
+    first = dicts[0]
+    if all(d == first for d in dicts[1:]) and \
+            all(first[i] <= first[i + 1] for i in range(len(first) - 1)):
+        return first, False
+    return sorted(set().union(*map(set, dicts))), True
+
+
+def string_remap_tables(merged: List[str], dicts: List[List[str]]):
+    """Per dictionary, the table old code -> code in ``merged``: None
+    when the dictionary IS ``merged`` (codes stay), [0] for an empty
+    dictionary (its codes are all masked zeros)."""
+    vi = {v: i for i, v in enumerate(merged)}
+    for d in dicts:
+        yield None if d == merged else ([vi[v] for v in d] or [0])
+
+
 def read_native_host(path: str, columns: Optional[List[str]] = None
                      ) -> Optional[Tuple[Dict[str, np.ndarray],
                                          Dict[str, np.ndarray]]]:
@@ -1052,16 +1101,14 @@ def read_native_host(path: str, columns: Optional[List[str]] = None
         if c.is_string:
             values = c.dict_values(data) if c.dict_page else []
             for page, mask in zip(c.pages, c.page_masks):
-                if page[0] == "splain":
-                    _, p_start, p_end, nv = page
-                    n_valid = int(mask.sum()) if mask is not None else nv
+                nv = page.num_values
+                n_valid = int(mask.sum()) if mask is not None else nv
+                if page.kind == "splain":
                     codes, page_vals = decode_splain_pages(
-                        data, [p_start], [p_end], [n_valid])
+                        data, [page.start], [page.end], [n_valid])
                 else:
-                    _, p_start, p_end, nv, bw = page
-                    n_valid = int(mask.sum()) if mask is not None else nv
-                    codes = _decode_rle_indices(data, p_start, p_end,
-                                                n_valid, bw)
+                    codes = _decode_rle_indices(data, page.start, page.end,
+                                                n_valid, page.bit_width)
                     page_vals = values
                 if mask is None:
                     part = codes
@@ -1077,25 +1124,23 @@ def read_native_host(path: str, columns: Optional[List[str]] = None
             continue
         dvals = None
         if c.dict_page is not None:
-            doff, dn = c.dict_page
-            dvals = np.frombuffer(data, dtype=c.np_dtype, count=dn,
-                                  offset=doff)
+            dvals = np.frombuffer(data, dtype=c.np_dtype,
+                                  count=c.dict_page.num_values,
+                                  offset=c.dict_page.start)
         for page, mask in zip(c.pages, c.page_masks):
-            if page[0] == "dict":
+            nv = page.num_values
+            n_valid = int(mask.sum()) if mask is not None else nv
+            if page.kind == "dict":
                 # numeric dictionary page (Spark's default output
                 # shape): decode indices, gather through the PLAIN
                 # dictionary values
-                _, p_start, p_end, nv, bw = page
-                n_valid = int(mask.sum()) if mask is not None else nv
-                idx = _decode_rle_indices(data, p_start, p_end,
-                                          n_valid, bw)
+                idx = _decode_rle_indices(data, page.start, page.end,
+                                          n_valid, page.bit_width)
                 vals = (dvals[idx] if n_valid
                         else np.empty(0, dtype=c.np_dtype))
             else:
-                _, off, nv = page
-                n_valid = int(mask.sum()) if mask is not None else nv
                 vals = np.frombuffer(data, dtype=c.np_dtype,
-                                     count=n_valid, offset=off)
+                                     count=n_valid, offset=page.start)
             if mask is None:
                 part = vals
                 pm = np.ones(nv, dtype=bool)
@@ -1109,23 +1154,17 @@ def read_native_host(path: str, columns: Optional[List[str]] = None
     cols: Dict[str, Any] = {}
     for name, parts in acc.items():
         if name in str_dicts:
-            dicts = str_dicts[name]
-            if all(d == dicts[0] for d in dicts[1:]) and \
-                    all(dicts[0][i] <= dicts[0][i + 1]
-                        for i in range(len(dicts[0]) - 1)):
-                merged_vals = dicts[0]
+            merged_vals, remap = merge_string_dicts(str_dicts[name])
+            if remap:  # per-row-group dictionaries
+                parts = [part if lut is None
+                         else np.array(lut, dtype=np.int32)[part]
+                         for part, lut in zip(parts, string_remap_tables(
+                             merged_vals, str_dicts[name]))]
+                codes = (np.concatenate(parts) if len(parts) > 1
+                         else parts[0])
+            else:
                 codes = (np.concatenate(parts) if len(parts) > 1
                          else parts[0].copy())
-            else:  # per-row-group dictionaries: merge + remap
-                merged_vals = sorted(set().union(*map(set, dicts)))
-                vi = {v: i for i, v in enumerate(merged_vals)}
-                remapped = []
-                for part, d in zip(parts, dicts):
-                    lut = np.array([vi[v] for v in d] or [0],
-                                   dtype=np.int32)
-                    remapped.append(lut[part])
-                codes = (np.concatenate(remapped) if len(remapped) > 1
-                         else remapped[0])
             if not merged_vals and len(codes):
                 # all-null column: masked slots carry code 0 — give it
                 # a value to dereference

@@ -18,7 +18,7 @@ print(f"layout: {time.time()-t0:.2f}s ->", "OK" if lay else "None")
 if lay:
     for c in lay[1]:
         kinds = {}
-        for pg in c.pages: kinds[pg[0]] = kinds.get(pg[0], 0) + 1
+        for pg in c.pages: kinds[pg.kind] = kinds.get(pg.kind, 0) + 1
         print(f"  {c.name}: enc={c.encoding} pages={kinds}")
 orig = parquet_io.read_files_batch
 def spy(*a, **k):

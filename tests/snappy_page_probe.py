@@ -43,11 +43,11 @@ def snappy_host_opstats(src):
 
 for c in chunks[:1]:  # key chunk of rg0
     segs = []
-    if c.encoding == "dict_z" and len(c.dict_page) == 5:
-        _, a, b, dn, unc = c.dict_page
-        segs.append(("dict", a, b, unc))
+    if c.encoding == "dict_z" and c.dict_page.compressed:
+        dp = c.dict_page
+        segs.append(("dict", dp.start, dp.end, dp.unc_size))
     for pg in c.pages[:6]:
-        segs.append((pg[0], pg[1], pg[2], pg[4]))
+        segs.append((pg.kind, pg.start, pg.end, pg.unc_size))
     for name, a, b, unc in segs:
         comp = b - a
         scratch = torch.empty(unc + 4, dtype=torch.uint8, device=dev)

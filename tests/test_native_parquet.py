@@ -173,28 +173,19 @@ def test_split_row_groups_boundaries():
     """The GPU decode's row-group splitter: layout order is row-group-
     major, so a repeated column name starts a new group and row offsets
     accumulate per group."""
-    from hyperspace_amd.sources.native_parquet import ColumnChunkLayout
+    from hyperspace_amd.sources.device_decode import split_row_groups
+    from hyperspace_amd.sources.native_parquet import (ColumnChunkLayout,
+                                                       Page)
     import numpy as np
 
     def chunk(name, nrows):
         return ColumnChunkLayout(name, np.dtype("int64"),
-                                 [("plain", 0, nrows)], nrows)
+                                 [Page("plain", 0, 8 * nrows, nrows)], nrows)
 
     chunks = [chunk("a", 10), chunk("b", 10),
               chunk("a", 7), chunk("b", 7),
               chunk("a", 3), chunk("b", 3)]
-    # reproduce the splitter used by read_files_batch_device
-    groups = []
-    cur, seen, row_off = [], set(), 0
-    for c in chunks:
-        if c.name in seen:
-            groups.append((row_off, cur))
-            row_off += cur[0].num_values
-            cur, seen = [], set()
-        cur.append(c)
-        seen.add(c.name)
-    if cur:
-        groups.append((row_off, cur))
+    groups = split_row_groups(chunks)
     assert [(off, [c.name for c in cs], cs[0].num_values)
             for off, cs in groups] == \
         [(0, ["a", "b"], 10), (10, ["a", "b"], 7), (17, ["a", "b"], 3)]

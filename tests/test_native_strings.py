@@ -176,7 +176,7 @@ def test_compressed_string_dict_overflow_layout(tmp_path):
                                        "RLE_DICTIONARY"}, encs
     lay = read_native_layout(p)
     assert lay is not None
-    kinds = {pg[0] for c in lay[1] for pg in c.pages}
+    kinds = {pg.kind for c in lay[1] for pg in c.pages}
     assert kinds == {"dict_z", "splain_z"}, kinds
     assert read_native_host(p) is None  # compressed: device-only
     rb, counts = read_files_batch([p])
@@ -230,7 +230,7 @@ def test_mixed_dict_plain_string_chunk_host(tmp_path):
                            dictionary_pagesize_limit=64 * 1024)
     lay = read_native_layout(p)
     assert lay is not None
-    kinds = {pg[0] for c in lay[1] for pg in c.pages}
+    kinds = {pg.kind for c in lay[1] for pg in c.pages}
     assert kinds == {"dict", "splain"}, kinds
     cols, _ = read_native_host(p)
     s = cols["s"]

@@ -264,7 +264,7 @@ def test_mixed_dict_plain_string_chunk_device_read(tmp_path):
                    data_page_version="1.0")
     from hyperspace_amd.sources.native_parquet import read_native_layout
     lay = read_native_layout(p)
-    kinds = {pg[0] for c in lay[1] for pg in c.pages}
+    kinds = {pg.kind for c in lay[1] for pg in c.pages}
     assert kinds == {"dict", "splain"}, kinds
     batch, rc = read_files_batch_device([p], torch.device("cuda:0"))
     assert rc == [300_000]
