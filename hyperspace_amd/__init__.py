@@ -17,8 +17,9 @@ Quick start::
     df.filter("key = 42").collect()     # served from the index
 """
 
+from . import functions
 from .config import Conf, IndexConstants
-from .dataframe import DataFrame
+from .dataframe import DataFrame, GroupedData
 from .exceptions import HyperspaceException, KernelUnavailableError
 from .hyperspace import Hyperspace
 from .index.covering import CoveringIndex, CoveringIndexConfig
@@ -30,7 +31,7 @@ from .index.dataskipping import (BloomFilterSketch, DataSkippingIndex,
                                  DataSkippingIndexConfig, MinMaxSketch,
                                  PartitionSketch)
 from .index.zorder import ZOrderCoveringIndex, ZOrderCoveringIndexConfig
-from .plan.expr import col, lit
+from .plan.expr import AggExpr, col, lit
 from .session import HyperspaceSession, get_session, set_session
 
 __version__ = "0.1.0"
@@ -43,4 +44,5 @@ __all__ = [
     "BloomFilterSketch", "PartitionSketch",
     "ZOrderCoveringIndex", "ZOrderCoveringIndexConfig",
     "get_session", "set_session",
+    "functions", "AggExpr", "GroupedData",
 ]

@@ -32,6 +32,8 @@ class IndexConstants:
     INDEX_LINEAGE_ENABLED = "spark.hyperspace.index.lineage.enabled"
     INDEX_FILTER_RULE_USE_BUCKET_SPEC = (
         "spark.hyperspace.index.filterRule.useBucketSpec")
+    INDEX_AGGREGATE_RULE_ENABLED = (
+        "spark.hyperspace.index.aggregateRule.enabled")
     OPTIMIZE_FILE_SIZE_THRESHOLD = (
         "spark.hyperspace.index.optimize.fileSizeThreshold")
     OPTIMIZE_FILE_SIZE_THRESHOLD_DEFAULT = 256 * 1024 * 1024
@@ -81,6 +83,7 @@ _DEFAULTS: Dict[str, Any] = {
         IndexConstants.INDEX_HYBRID_SCAN_DELETED_RATIO_THRESHOLD_DEFAULT,
     IndexConstants.INDEX_LINEAGE_ENABLED: False,
     IndexConstants.INDEX_FILTER_RULE_USE_BUCKET_SPEC: False,
+    IndexConstants.INDEX_AGGREGATE_RULE_ENABLED: True,
     IndexConstants.OPTIMIZE_FILE_SIZE_THRESHOLD:
         IndexConstants.OPTIMIZE_FILE_SIZE_THRESHOLD_DEFAULT,
     IndexConstants.APPLY_HYPERSPACE_ENABLED: True,
@@ -158,6 +161,10 @@ class Conf:
     @property
     def filter_rule_use_bucket_spec(self) -> bool:
         return bool(self.get(IndexConstants.INDEX_FILTER_RULE_USE_BUCKET_SPEC))
+
+    @property
+    def aggregate_rule_enabled(self) -> bool:
+        return bool(self.get(IndexConstants.INDEX_AGGREGATE_RULE_ENABLED))
 
     @property
     def optimize_file_size_threshold(self) -> int:

@@ -680,6 +680,128 @@ torch::Tensor gather_rows(torch::Tensor values, torch::Tensor idx) {
   return out;
 }
 
+// The group-by kernels read 16-byte vectors: a contiguous view that
+// starts mid-allocation (a slice) is copied to an aligned buffer.
+torch::Tensor aligned16(torch::Tensor t) {
+  if (t.numel() > 0 && reinterpret_cast<uintptr_t>(t.data_ptr()) % 16 != 0)
+    return t.clone();
+  return t;
+}
+
+// Group offsets of adjacent equal rows: int64 [n_groups + 1].  keys: 1..8
+// normalized u64 columns (int64-encoded); masks: empty, or parallel to
+// keys with empty tensors for columns without nulls.
+torch::Tensor group_offsets(std::vector<torch::Tensor> keys,
+                            std::vector<torch::Tensor> masks) {
+  TORCH_CHECK(!keys.empty() && keys.size() <= 8, "1..8 key columns");
+  TORCH_CHECK(masks.empty() || masks.size() == keys.size(),
+              "masks must be empty or parallel to keys");
+  int64_t n = keys[0].numel();
+  auto dev = keys[0].device();
+  auto opts = torch::dtype(torch::kInt64).device(dev);
+  if (n == 0) return torch::zeros({1}, opts);
+  std::vector<torch::Tensor> held;
+  const uint64_t* kptr[8] = {nullptr};
+  const uint8_t* mptr[8] = {nullptr};
+  for (size_t c = 0; c < keys.size(); ++c) {
+    check_cuda(keys[c], "key");
+    TORCH_CHECK(keys[c].scalar_type() == torch::kInt64,
+                "keys must be normalized int64");
+    TORCH_CHECK(keys[c].numel() == n, "key column length mismatch");
+    held.push_back(aligned16(keys[c]));
+    kptr[c] = (const uint64_t*)held.back().data_ptr<int64_t>();
+    if (!masks.empty() && masks[c].numel() > 0) {
+      check_cuda(masks[c], "mask");
+      TORCH_CHECK(masks[c].numel() == n, "mask length mismatch");
+      TORCH_CHECK(masks[c].scalar_type() == torch::kBool ||
+                      masks[c].scalar_type() == torch::kUInt8,
+                  "mask must be bool/uint8");
+      held.push_back(aligned16(masks[c]));
+      mptr[c] = (const uint8_t*)held.back().data_ptr();
+    }
+  }
+  auto stream = current_stream();
+  int64_t tile = hsk::group_tile_size();
+  int64_t n_tiles = (n + tile - 1) / tile;
+  auto tile_counts = torch::empty({n_tiles}, opts);
+  hsk::group_offsets_count(kptr, mptr, (int)keys.size(), n,
+                           tile_counts.data_ptr<int64_t>(), stream);
+  auto tile_offsets = torch::empty({n_tiles}, opts);
+  auto total = torch::empty({1}, opts);
+  hsk::exclusive_scan_i64(tile_counts.data_ptr<int64_t>(),
+                          tile_offsets.data_ptr<int64_t>(), n_tiles,
+                          total.data_ptr<int64_t>(), stream);
+  int64_t n_groups = total.cpu().item<int64_t>();
+  auto out = torch::empty({n_groups + 1}, opts);
+  hsk::group_offsets_emit(kptr, mptr, (int)keys.size(), n,
+                          tile_offsets.data_ptr<int64_t>(),
+                          total.data_ptr<int64_t>(), out.data_ptr<int64_t>(),
+                          stream);
+  return out;
+}
+
+// Fused segmented reduce: (sum, min, max, count) per group; want is a
+// bit set (1 sum, 2 min, 4 max) — a tensor not asked for comes back
+// empty.  count is always computed.  valid: empty = no nulls.
+std::vector<torch::Tensor> segmented_reduce(torch::Tensor values,
+                                            torch::Tensor valid,
+                                            torch::Tensor offsets,
+                                            int64_t want) {
+  check_cuda(values, "values");
+  int dtype;
+  switch (values.scalar_type()) {
+    case torch::kInt64: dtype = 0; break;
+    case torch::kInt32: dtype = 1; break;
+    case torch::kFloat64: dtype = 2; break;
+    case torch::kFloat32: dtype = 3; break;
+    default:
+      TORCH_CHECK(false, "segmented_reduce: values must be int32, int64, "
+                         "float32 or float64");
+  }
+  bool is_float = dtype >= 2;
+  auto dev = values.device();
+  int64_t n = values.numel();
+  auto off_d = offsets.to(dev, torch::kInt64).contiguous();
+  TORCH_CHECK(off_d.numel() >= 1, "offsets must have n_groups + 1 entries");
+  int64_t n_groups = off_d.numel() - 1;
+  auto i64 = torch::dtype(torch::kInt64).device(dev);
+  auto sum_opts = is_float ? torch::dtype(torch::kFloat64).device(dev) : i64;
+  // zero-filled: a group the kernel never closes (possible only with
+  // malformed offsets) reads as empty
+  auto sums = torch::zeros({(want & 1) ? n_groups : 0}, sum_opts);
+  auto mins = torch::zeros({(want & 2) ? n_groups : 0}, values.options());
+  auto maxs = torch::zeros({(want & 4) ? n_groups : 0}, values.options());
+  auto counts = torch::zeros({n_groups}, i64);
+  if (n == 0 || n_groups == 0) return {sums, mins, maxs, counts};
+  values = aligned16(values);
+  const uint8_t* vptr = nullptr;
+  if (valid.numel() > 0) {
+    check_cuda(valid, "valid");
+    TORCH_CHECK(valid.numel() == n, "valid length mismatch");
+    TORCH_CHECK(valid.scalar_type() == torch::kBool ||
+                    valid.scalar_type() == torch::kUInt8,
+                "valid must be bool/uint8");
+    valid = aligned16(valid);
+    vptr = (const uint8_t*)valid.data_ptr();
+  }
+  int64_t tile = hsk::group_tile_size();
+  int64_t n_tiles = (n + tile - 1) / tile;
+  auto tile_groups = torch::empty({n_tiles + 1}, i64);
+  auto partials =
+      torch::empty({4 * hsk::segmented_reduce_num_blocks(n)}, i64);
+  hsk::segmented_reduce(values.data_ptr(), dtype, vptr,
+                        off_d.data_ptr<int64_t>(), n, n_groups,
+                        (want & 1) ? sums.data_ptr() : nullptr,
+                        (want & 2) ? mins.data_ptr() : nullptr,
+                        (want & 4) ? maxs.data_ptr() : nullptr,
+                        counts.data_ptr<int64_t>(),
+                        tile_groups.data_ptr<int64_t>(),
+                        partials.data_ptr<int64_t>(), current_stream());
+  return {sums, mins, maxs, counts};
+}
+
+int64_t group_tile_size() { return hsk::group_tile_size(); }
+
 }  // namespace
 
 // out-of-namespace impl so the two-phase select is a single public symbol
@@ -740,6 +862,13 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         "device parquet page decode (unaligned copy)");
   m.def("run_merge_perm", &run_merge_perm,
         "segmented two-sorted-run merge permutation");
+  m.def("group_offsets", &group_offsets,
+        "offsets of adjacent equal-key runs: int64 [n_groups + 1]",
+        py::arg("keys"), py::arg("masks") = std::vector<torch::Tensor>{});
+  m.def("segmented_reduce", &segmented_reduce,
+        "fused per-group (sum, min, max, count); want bits 1/2/4");
+  m.def("group_tile_size", &group_tile_size,
+        "rows per tile of the group-by kernels");
   m.def("snappy_decompress", &snappy_decompress,
         "device snappy raw-block page decompression; returns status");
   m.def("decode_def_levels", &decode_def_levels,

@@ -1,5 +1,6 @@
 // Host-side API of the CDNA4 kernel suite (pure HIP, gfx950).
-// Implemented in kernels.hip; called from the torch binding (binding.cpp).
+// Implemented in kernels.hip and aggregate.hip; called from the torch
+// binding (binding.cpp).
 #pragma once
 
 #include <cstdint>
@@ -105,6 +106,41 @@ void isin_sorted(const int64_t* vals, int64_t n, const int64_t* sorted_set,
 // K8: per-segment min/max of int64 values
 void segmented_minmax(const int64_t* vals, const int64_t* seg_off,
                       int64_t n_seg, int64_t* mins, int64_t* maxs,
+                      hipStream_t stream);
+
+// K13 (aggregate.hip): group-by over adjacent runs.  Both ops tile the
+// ROWS (group_tile_size() rows per tile), never the groups.
+int64_t group_tile_size();
+// group offsets, two-phase like select_range: count writes the number of
+// group heads per tile; after an exclusive scan of the tile counts
+// (exclusive_scan_i64, total = n_groups) emit writes the head row of every
+// group in ascending order and out[n_groups] = n.  keys: 1..8 host arrays
+// of device pointers to normalized u64 columns; masks: nullptr, or per
+// column validity bytes / nullptr.  Row i heads a group if i == 0 or any
+// column's (null flag, key) differs from row i - 1; the stored key of a
+// null row is ignored.  Key and mask pointers must be 16-byte aligned.
+void group_offsets_count(const uint64_t* const* keys,
+                         const uint8_t* const* masks, int n_cols, int64_t n,
+                         int64_t* tile_counts, hipStream_t stream);
+void group_offsets_emit(const uint64_t* const* keys,
+                        const uint8_t* const* masks, int n_cols, int64_t n,
+                        const int64_t* tile_offsets, const int64_t* total,
+                        int64_t* out, hipStream_t stream);
+// fused segmented reduce: per group [offsets[g], offsets[g+1]) the sum,
+// min, max and valid-count of vals in one read.  dtype: 0=i64, 1=i32,
+// 2=f64, 3=f32.  sums are i64 (wrapping) for integers and f64 for floats;
+// mins/maxs have the input type and follow normalize_key order; any of
+// sums/mins/maxs may be null, counts is required.  A group with no valid
+// row gets count 0 and zeros.  valid: validity bytes or nullptr.  offsets
+// must ascend strictly from 0 to n.  tile_groups: n_tiles + 1 scratch
+// entries; partials: 4 * segmented_reduce_num_blocks(n) scratch entries.
+// vals and valid must be 16-byte aligned.  No atomics: float sums are
+// bitwise reproducible.
+int64_t segmented_reduce_num_blocks(int64_t n);
+void segmented_reduce(const void* vals, int dtype, const uint8_t* valid,
+                      const int64_t* offsets, int64_t n, int64_t n_groups,
+                      void* sums, void* mins, void* maxs, int64_t* counts,
+                      int64_t* tile_groups, int64_t* partials,
                       hipStream_t stream);
 
 // K8: bloom filter build/probe (k hashes, m_bits bits over u64 words)

@@ -1,16 +1,18 @@
 """User-facing DataFrame: a logical plan + session.
 
 Mirrors the subset of the Spark DataFrame surface that Hyperspace's API
-touches: filter / select / join / collect, plus plan access for
+touches: filter / select / join / group_by / agg / distinct / collect,
+plus plan access for
 createIndex, explain and whyNot.
 """
 
 from __future__ import annotations
 
-from typing import List, Optional, Union
+from typing import Dict, List, Optional, Union
 
-from .plan.expr import Expr, col as _col, parse_predicate
-from .plan.nodes import Filter, Join, LogicalPlan, Project
+from .exceptions import HyperspaceException
+from .plan.expr import AggExpr, Col, Expr, col as _col, parse_predicate
+from .plan.nodes import Aggregate, Filter, Join, LogicalPlan, Project
 
 
 class DataFrame:
@@ -57,6 +59,25 @@ class DataFrame:
         return DataFrame(self.session,
                          Join(self.plan, other.plan, condition, how))
 
+    def group_by(self, *cols: Union[str, Col]) -> "GroupedData":
+        """Group by columns; finish with ``.agg(...)`` or ``.count()``.
+        Null keys compare equal and form one group.  Grouping on float
+        columns is refused when the query runs."""
+        return GroupedData(self, _resolve_columns(self.plan, cols))
+
+    groupBy = group_by
+
+    def agg(self, *aggs: Union[AggExpr, Dict[str, str]]) -> "DataFrame":
+        """Global aggregate (no keys): exactly one row, also on empty
+        input, where counts are 0 and every other aggregate is null."""
+        return GroupedData(self, []).agg(*aggs)
+
+    def distinct(self) -> "DataFrame":
+        """Distinct rows: an aggregate over all output columns with no
+        aggregate expressions."""
+        return DataFrame(self.session, Aggregate(
+            self.plan.output_columns(), [], self.plan))
+
     # -- actions ----------------------------------------------------------
     def optimized_plan(self) -> LogicalPlan:
         """Apply the Hyperspace rewrite rules if enabled."""
@@ -84,6 +105,61 @@ class DataFrame:
 
     def __repr__(self):
         return f"DataFrame:\n{self.plan.pretty()}"
+
+
+class GroupedData:
+    """``df.group_by(...)``: holds the grouping columns until ``agg``."""
+
+    def __init__(self, df: DataFrame, group_cols: List[str]):
+        self._df = df
+        self._group_cols = group_cols
+
+    def agg(self, *aggs: Union[AggExpr, Dict[str, str]]) -> DataFrame:
+        """Aggregate each group.  Takes ``AggExpr`` objects from
+        ``hyperspace_amd.functions`` or the pyspark dict form
+        ``{"column": "function"}`` (``{"*": "count"}`` counts rows).
+        Output: the grouping columns, then one column per aggregate, in
+        unspecified row order."""
+        exprs: List[AggExpr] = []
+        for a in aggs:
+            if isinstance(a, dict):
+                exprs.extend(AggExpr(f, c) for c, f in a.items())
+            elif isinstance(a, AggExpr):
+                exprs.append(a)
+            else:
+                raise HyperspaceException(
+                    f"agg() takes AggExpr objects or a dict, got {a!r}")
+        if not exprs:
+            raise HyperspaceException("agg() needs at least one aggregate")
+        plan = self._df.plan
+        resolved = [
+            e if e.column is None
+            else e.with_column(_resolve_columns(plan, [e.column])[0])
+            for e in exprs]
+        seen = set()
+        for name in self._group_cols + [e.output_name for e in resolved]:
+            if name.lower() in seen:
+                raise HyperspaceException(
+                    f"Duplicate output column {name!r} in aggregate")
+            seen.add(name.lower())
+        return DataFrame(self._df.session,
+                         Aggregate(self._group_cols, resolved, plan))
+
+    def count(self) -> DataFrame:
+        return self.agg(AggExpr("count"))
+
+
+def _resolve_columns(plan: LogicalPlan, cols) -> List[str]:
+    """Names as the plan spells them (matched case-insensitively)."""
+    have = {c.lower(): c for c in plan.output_columns()}
+    out = []
+    for c in cols:
+        name = c.name if isinstance(c, Col) else c
+        if not isinstance(name, str) or name.lower() not in have:
+            raise HyperspaceException(
+                f"No column {name!r}; have {plan.output_columns()}")
+        out.append(have[name.lower()])
+    return out
 
 
 def _bind_decimal_literals(cond: Expr, plan: LogicalPlan) -> Expr:

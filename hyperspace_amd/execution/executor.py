@@ -11,6 +11,9 @@ Operator -> data-plane mapping:
   Join            K4  per-bucket merge join (zero exchange when co-bucketed)
   IndexScan       bucket-pruned index read (FilterIndexRule target)
   BucketUnionNode K5  partition-aligned concat (+ per-bucket re-sort)
+  Aggregate       K13 group_offsets + fused segmented_reduce over adjacent
+                      runs (no sort, no exchange, when the child is
+                      bucketed on the grouping column)
 """
 
 from __future__ import annotations
@@ -26,8 +29,8 @@ from ..config import IndexConstants
 from ..exceptions import HyperspaceException
 from ..plan.expr import (And, BinComp, Col, Expr, In, IsNotNull, IsNull,
                          Lit, Not, Or, extract_equi_join_keys)
-from ..plan.nodes import (BucketUnionNode, Filter, IndexScan, Join,
-                          LogicalPlan, Project, Scan, UnionNode)
+from ..plan.nodes import (Aggregate, BucketUnionNode, Filter, IndexScan,
+                          Join, LogicalPlan, Project, Scan, UnionNode)
 from ..sources.parquet_io import (read_files_batch,
                                   read_files_batch_device,
                                   bucket_id_of_file)
@@ -43,6 +46,7 @@ class PhysicalStats:
         self.shuffles = 0          # on-the-fly repartitions (Exchange analog)
         self.merge_joins = 0
         self.hash_joins = 0
+        self.sort_aggregates = 0
         self.bucket_pruned_files = 0
         self.operators: List[str] = []
 
@@ -86,6 +90,8 @@ class Executor:
             return self._exec_join(plan), None
         if isinstance(plan, BucketUnionNode):
             return self._exec_bucket_union(plan)
+        if isinstance(plan, Aggregate):
+            return self._exec_aggregate(plan), None
         if isinstance(plan, UnionNode):
             self.stats.record("Union")
             parts = [self._exec(c)[0] for c in plan.children]
@@ -635,6 +641,60 @@ class Executor:
                              ColumnBatch.concat([p[1] for p in pieces]))
 
     # ------------------------------------------------------------------
+    def _exec_aggregate(self, plan: Aggregate) -> ColumnBatch:
+        """Group-by as a reduce over adjacent runs (K13).
+
+        Grouped path: the child is bucketed on the single grouping
+        column, so every group sits in one bucket with its rows adjacent
+        (filters and projections keep row order) — no sort, no
+        repartition.  Multi-file buckets are re-sorted on the stored
+        placeholder of null rows, so null keys are split off and reduced
+        as one group of their own.  Sort path (everything else): sort by
+        the grouping columns first, which counts as a shuffle.  A global
+        aggregate is one run and needs neither."""
+        batch, _ = self._exec(plan.child)
+        keys = plan.group_cols
+        for k in keys:
+            col = batch.column(k)
+            if not isinstance(col, StringColumn) and \
+                    col.dtype.is_floating_point:
+                raise HyperspaceException(
+                    f"Grouping on float column {k!r} is not supported: "
+                    "-0.0 / +0.0 and NaN need SQL equality rules the "
+                    "adjacent-run grouping does not apply yet")
+        op = aggregate_operator_name(plan)
+        self.stats.sort_aggregates += 1
+        self.stats.record(op)
+        if not keys:
+            return _reduce_runs(batch, [], plan.aggs, global_group=True)
+        if op == "SortAggregate(bucketed)":
+            if batch.has_nulls(keys[0]):
+                rest, _, nulls = _split_null_keys(batch, keys[0], None)
+                return ColumnBatch.concat([
+                    _reduce_runs(rest, keys, plan.aggs),
+                    _reduce_runs(nulls, keys, plan.aggs, one_group=True)])
+            return _reduce_runs(batch, keys, plan.aggs)
+        self.stats.shuffles += 1
+        if batch.num_rows:
+            from ..index.covering.index import _multi_key_sort_perm
+            # null rows sort on (null flag, key): blank their stored
+            # values so equal key tuples end up adjacent
+            sort_batch = batch.select(keys)
+            for k in keys:
+                m = batch.mask(k)
+                if m is not None and not bool(m.all()):
+                    t = sort_batch.tensor(k)
+                    t = torch.where(m, t, torch.zeros((), dtype=t.dtype,
+                                                      device=t.device))
+                    c = sort_batch.column(k)
+                    sort_batch = sort_batch.with_column(
+                        sort_batch._stored_key(k),
+                        StringColumn(t, c.values)
+                        if isinstance(c, StringColumn) else t, m)
+            batch = batch.gather(_multi_key_sort_perm(sort_batch, keys))
+        return _reduce_runs(batch, keys, plan.aggs)
+
+    # ------------------------------------------------------------------
     def _exec_bucket_union(self, plan: BucketUnionNode
                            ) -> Tuple[ColumnBatch, Optional[torch.Tensor]]:
         """Partition-aligned union: concatenate same-bucket segments from
@@ -815,6 +875,123 @@ def _typed_match(mode: str, lk: torch.Tensor, rk: torch.Tensor,
         return unmatched, none
     return (torch.cat([lidx, unmatched]),
             torch.cat([ridx, torch.full_like(unmatched, -1)]))
+
+
+def _bucketed_group_source(plan: LogicalPlan, key: str) -> bool:
+    """True if the subplan, walked down through Project and Filter nodes
+    (both keep row order), is a bucketed covering IndexScan whose single
+    indexed column is ``key``, or a BucketUnion on exactly that column:
+    every group then lies inside one bucket with its rows adjacent."""
+    node = plan
+    while isinstance(node, (Project, Filter)):
+        node = node.child
+    if isinstance(node, IndexScan):
+        index = node.entry.derivedDataset
+        return (node.use_bucket_spec and index.kind == "CoveringIndex" and
+                [c.lower() for c in index.indexed_columns] == [key.lower()])
+    if isinstance(node, BucketUnionNode):
+        return [c.lower() for c in node.bucket_columns] == [key.lower()]
+    return False
+
+
+def aggregate_operator_name(plan: Aggregate) -> str:
+    """Physical operator an Aggregate node runs as."""
+    if not plan.group_cols:
+        return "SortAggregate(global)"
+    if len(plan.group_cols) == 1 and \
+            _bucketed_group_source(plan.child, plan.group_cols[0]):
+        return "SortAggregate(bucketed)"
+    return "SortAggregate(shuffled)"
+
+
+_REDUCE_OUTPUTS = {"sum": ("sum", "count"), "avg": ("sum", "count"),
+                   "min": ("min", "count"), "max": ("max", "count"),
+                   "count": ("count",)}
+
+
+def _reduce_runs(batch: ColumnBatch, keys: List[str], aggs,
+                 one_group: bool = False, global_group: bool = False
+                 ) -> ColumnBatch:
+    """Aggregate runs of adjacent equal ``keys`` rows: group offsets from
+    adjacency, then one fused segmented reduce per input column.
+    ``one_group``: all rows are one group (the null-key rows);
+    ``global_group``: likewise, and an empty input still gives one row."""
+    n = batch.num_rows
+    dev = batch.device
+    if global_group or one_group:
+        n_groups = 1 if (n or global_group) else 0
+        offsets = torch.tensor([0, n] if n_groups else [0],
+                               dtype=torch.int64, device=dev)
+    elif n == 0:
+        offsets = torch.zeros(1, dtype=torch.int64, device=dev)
+    else:
+        masks = [batch.mask(k) for k in keys]
+        offsets = ops.group_offsets(
+            [ops.normalize_key(batch.tensor(k)) for k in keys],
+            masks if any(m is not None for m in masks) else None)
+    n_groups = offsets.numel() - 1
+    first = offsets[:-1]
+    cols: Dict[str, object] = {}
+    masks_out: Dict[str, torch.Tensor] = {}
+    for k in keys:
+        name = batch._stored_key(k)
+        c = batch.column(k)
+        cols[name] = c.gather(first) if isinstance(c, StringColumn) \
+            else ops.gather_rows(c, first)
+        m = batch.mask(k)
+        if m is not None:
+            masks_out[name] = m[first]
+
+    # one fused reduce per input column, for everything asked of it
+    wanted: Dict[str, set] = {}
+    for a in aggs:
+        if a.column is not None:
+            wanted.setdefault(a.column.lower(), set()).update(
+                _REDUCE_OUTPUTS[a.func])
+    reduced: Dict[str, dict] = {}
+    for cname, outs in wanted.items():
+        c = batch.column(cname)
+        if isinstance(c, StringColumn) and outs & {"sum"}:
+            raise HyperspaceException(
+                f"sum/avg over string column {cname!r} is not supported")
+        want = tuple(o for o in ("sum", "min", "max", "count") if o in outs)
+        if n == 0:
+            # nothing to read: counts are 0, everything else null
+            t = batch.tensor(cname)
+            sum_dt = torch.float64 if t.dtype.is_floating_point \
+                else torch.int64
+            reduced[cname] = {
+                o: torch.zeros(n_groups, device=dev, dtype=(
+                    sum_dt if o == "sum" else
+                    torch.int64 if o == "count" else t.dtype))
+                for o in want}
+        else:
+            reduced[cname] = ops.segmented_reduce(
+                batch.tensor(cname), batch.mask(cname), offsets, want)
+    for a in aggs:
+        name = a.output_name
+        if a.column is None:
+            cols[name] = offsets[1:] - offsets[:-1]
+            continue
+        c = batch.column(a.column)
+        r = reduced[a.column.lower()]
+        cnt = r["count"]
+        if a.func == "count":
+            cols[name] = cnt
+            continue
+        if a.func == "sum":
+            out = r["sum"]
+        elif a.func == "avg":
+            out = r["sum"].to(torch.float64) / cnt.to(torch.float64)
+        else:
+            t = c.codes if isinstance(c, StringColumn) else c
+            out = r[a.func].to(t.dtype)
+            if isinstance(c, StringColumn):
+                out = StringColumn(out, c.values if len(c.values) else [""])
+        cols[name] = out
+        if batch.mask(a.column) is not None or n == 0:
+            masks_out[name] = cnt > 0
+    return ColumnBatch(cols, masks_out)
 
 
 def _null_batch(like: ColumnBatch, n: int) -> ColumnBatch:

@@ -16,6 +16,8 @@ Op -> reference data-plane mapping:
   segmented_minmax K8  data-skipping MinMax sketch
   bloom_build/probe K8 data-skipping BloomFilter sketch
   zorder_key       K10 z-address bit interleave
+  group_offsets    K13 group-by: offsets of adjacent equal-key runs
+  segmented_reduce K13 group-by: fused per-group sum/min/max/count
   (extension-only: copy_unaligned/rle_decode/snappy_decompress — the K1
   parquet page decode surface used by sources/parquet_io.py)
 """
@@ -33,6 +35,7 @@ __all__ = [
     "murmur3_bucket", "normalize_key", "sort_pairs", "sort_perm",
     "merge_join", "run_merge_perm", "select_range_u64", "isin_sorted", "segmented_minmax",
     "bloom_build", "bloom_probe", "bloom_probe_many", "zorder_key", "gather_rows", "native",
+    "group_offsets", "segmented_reduce", "group_tile_size",
 ]
 
 
@@ -167,3 +170,62 @@ def zorder_key(cols_u64: List[torch.Tensor], bits_per_col: int
     if _is_cuda(*cols_u64):
         return native.ext().zorder_key(list(cols_u64), bits_per_col)
     return cpu_ref.zorder_key(cols_u64, bits_per_col)
+
+
+def group_tile_size() -> int:
+    """Rows per tile of the device group-by kernels (tests aim at it)."""
+    return int(native.ext().group_tile_size())
+
+
+def group_offsets(keys: List[torch.Tensor], masks=None) -> torch.Tensor:
+    """Offsets [n_groups + 1] (int64) of the runs of adjacent equal rows.
+
+    ``keys``: one to eight normalize_key()-ed columns.  ``masks``:
+    optional list parallel to keys of validity tensors or None.  A row
+    starts a group if it is row 0 or any column's (null flag, key) differs
+    from the previous row; the stored value of a null row is ignored."""
+    if not 1 <= len(keys) <= 8:
+        raise ValueError("group_offsets takes one to eight key columns")
+    if _is_cuda(*keys):
+        dev = keys[0].device
+        klist = [k.contiguous() for k in keys]
+        if masks is not None and any(m is not None for m in masks):
+            mlist = [(m.contiguous() if m is not None
+                      else torch.empty(0, dtype=torch.bool, device=dev))
+                     for m in masks]
+            return native.ext().group_offsets(klist, mlist)
+        return native.ext().group_offsets(klist)
+    return cpu_ref.group_offsets(keys, masks)
+
+
+_WANT_BITS = {"sum": 1, "min": 2, "max": 4, "count": 0}
+
+
+def segmented_reduce(values: torch.Tensor, valid, offsets: torch.Tensor,
+                     want=cpu_ref.SEGMENTED_REDUCE_OUTPUTS) -> dict:
+    """Fused per-group reduce over ``offsets`` (as group_offsets gives
+    them): a dict with the entries of ``want`` among ``sum`` (int64 with
+    wrap-around for integers, float64 for floats), ``min`` / ``max`` (the
+    input dtype, normalize_key order) and ``count`` (valid rows), all from
+    one read of ``values``.  ``valid`` is a validity tensor or None.
+    int8/int16/bool values are widened to int32 here."""
+    for w in want:
+        if w not in _WANT_BITS:
+            raise ValueError(f"segmented_reduce: unknown output {w!r}")
+    if values.dtype in (torch.int8, torch.int16, torch.bool, torch.uint8):
+        values = values.to(torch.int32)
+    if values.dtype not in (torch.int32, torch.int64, torch.float32,
+                            torch.float64):
+        raise ValueError(
+            f"segmented_reduce: unsupported dtype {values.dtype}")
+    if _is_cuda(values):
+        bits = 0
+        for w in want:
+            bits |= _WANT_BITS[w]
+        v = (valid.contiguous() if valid is not None
+             else torch.empty(0, dtype=torch.bool, device=values.device))
+        s, mn, mx, cnt = native.ext().segmented_reduce(
+            values.contiguous(), v, offsets, bits)
+        full = {"sum": s, "min": mn, "max": mx, "count": cnt}
+        return {w: full[w] for w in want}
+    return cpu_ref.segmented_reduce(values, valid, offsets.cpu(), want)

@@ -343,3 +343,88 @@ def run_merge_perm(keys_u64: torch.Tensor, seg: torch.Tensor,
         perm[a0 + pos_a] = torch.arange(a0, sp)
         perm[a0 + pos_b] = torch.arange(sp, b1)
     return perm
+
+
+# ---------------------------------------------------------------------------
+# Group-by over adjacent runs (K13)
+# ---------------------------------------------------------------------------
+
+def denormalize_key(keys_u64: torch.Tensor, dtype: torch.dtype
+                    ) -> torch.Tensor:
+    """Inverse of ``normalize_key`` for int32/int64/float32/float64."""
+    sign = -0x8000000000000000
+    if dtype in (torch.int32, torch.int64):
+        return (keys_u64 ^ sign).to(dtype)
+    # a set top bit marks a non-negative float (only its sign was flipped)
+    bits = torch.where(keys_u64 < 0, keys_u64 ^ sign, ~keys_u64)
+    return bits.view(torch.float64).to(dtype)
+
+
+def group_offsets(keys: List[torch.Tensor],
+                  masks: Optional[List[Optional[torch.Tensor]]] = None
+                  ) -> torch.Tensor:
+    """Offsets [n_groups + 1] of runs of adjacent equal rows.
+
+    ``keys`` are normalize_key() columns; ``masks[i]`` is a validity
+    tensor or None.  Row i starts a group if i == 0 or any column's
+    (null flag, key) differs from row i - 1; the stored key of a null row
+    is ignored, so adjacent nulls of a column compare equal."""
+    n = keys[0].numel()
+    if n == 0:
+        return torch.zeros(1, dtype=torch.int64)
+    head = torch.zeros(n, dtype=torch.bool)
+    head[0] = True
+    for ci, k in enumerate(keys):
+        m = masks[ci] if masks is not None else None
+        diff = k[1:] != k[:-1]
+        if m is not None and m.numel():
+            mb = m.to(torch.bool)
+            diff = (mb[1:] != mb[:-1]) | (mb[1:] & diff)
+        head[1:] |= diff
+    starts = torch.nonzero(head, as_tuple=False).flatten()
+    return torch.cat([starts, torch.tensor([n], dtype=torch.int64)])
+
+
+SEGMENTED_REDUCE_OUTPUTS = ("sum", "min", "max", "count")
+
+
+def segmented_reduce(values: torch.Tensor, valid: Optional[torch.Tensor],
+                     offsets: torch.Tensor,
+                     want=SEGMENTED_REDUCE_OUTPUTS) -> dict:
+    """Per group [offsets[g], offsets[g+1]): ``sum`` (int64 with
+    wrap-around for integers, float64 for floats), ``min`` / ``max`` (input
+    dtype, normalize_key order, so -0.0 < +0.0 and NaN sorts outermost)
+    and ``count`` of the valid rows.  Null rows (valid False) take no part;
+    a group without a valid row has count 0 and zeros elsewhere.  A float
+    sum starts from +0.0.  Returns a dict with the names in ``want``."""
+    offsets = offsets.to(torch.int64)
+    G = offsets.numel() - 1
+    n = values.numel()
+    is_float = values.dtype.is_floating_point
+    acc = torch.float64 if is_float else torch.int64
+    gid = torch.repeat_interleave(torch.arange(G, dtype=torch.int64),
+                                  offsets[1:] - offsets[:-1])
+    v = (valid.to(torch.bool) if valid is not None and valid.numel()
+         else torch.ones(n, dtype=torch.bool))
+    out = {}
+    cnt = torch.zeros(G, dtype=torch.int64).index_add_(
+        0, gid, v.to(torch.int64))
+    if "count" in want:
+        out["count"] = cnt
+    if "sum" in want:
+        x = torch.where(v, values.to(acc), torch.zeros((), dtype=acc))
+        out["sum"] = torch.zeros(G, dtype=acc).index_add_(0, gid, x)
+    if "min" in want or "max" in want:
+        sortable = _as_unsigned_sortable(normalize_key(values))
+        empty = cnt == 0
+        for name, red, ident in (
+                ("min", "amin", 0x7FFFFFFFFFFFFFFF),
+                ("max", "amax", -0x8000000000000000)):
+            if name not in want:
+                continue
+            s = torch.where(v, sortable, torch.full_like(sortable, ident))
+            r = torch.full((G,), ident, dtype=torch.int64).scatter_reduce_(
+                0, gid, s, red, include_self=True)
+            val = denormalize_key(_as_unsigned_sortable(r), values.dtype)
+            out[name] = torch.where(empty, torch.zeros_like(val), val)
+    return out

@@ -1,4 +1,4 @@
-from .expr import (And, BinComp, Col, Expr, In, IsNotNull, Lit, Not, Or,
+from .expr import (AggExpr, And, BinComp, Col, Expr, In, IsNotNull, Lit, Not, Or,
                    col, lit, parse_predicate)
-from .nodes import (BucketUnionNode, Filter, IndexScan, Join, LogicalPlan,
+from .nodes import (Aggregate, BucketUnionNode, Filter, IndexScan, Join, LogicalPlan,
                     Project, Scan)

@@ -247,6 +247,54 @@ class IsNull(Expr):
         return f"({self.col!r} IS NULL)"
 
 
+AGG_FUNCS = ("count", "sum", "min", "max", "avg")
+
+
+class AggExpr:
+    """One aggregate of a group-by: ``func`` over ``column`` (None only
+    for ``count()``, the row count), named ``alias`` in the output.
+    Built by ``hyperspace_amd.functions``; not a row-level ``Expr``."""
+
+    def __init__(self, func: str, column: "Union[str, Col, None]" = None,
+                 alias: "Union[str, None]" = None):
+        key = func.strip().lower() if isinstance(func, str) else None
+        if key not in AGG_FUNCS:
+            raise HyperspaceException(
+                f"Unknown aggregate function {func!r}; expected one of "
+                f"{list(AGG_FUNCS)}")
+        if isinstance(column, Col):
+            column = column.name
+        if column in ("*", 1):
+            column = None
+        if column is None and key != "count":
+            raise HyperspaceException(f"{key}() needs a column")
+        self.func = key
+        self.column = column
+        self.alias_name = alias
+
+    def alias(self, name: str) -> "AggExpr":
+        return AggExpr(self.func, self.column, name)
+
+    @property
+    def default_name(self) -> str:
+        return f"{self.func}({self.column if self.column is not None else 1})"
+
+    @property
+    def output_name(self) -> str:
+        return self.alias_name or self.default_name
+
+    def references(self) -> Set[str]:
+        return set() if self.column is None else {self.column}
+
+    def with_column(self, column: str) -> "AggExpr":
+        return AggExpr(self.func, column, self.alias_name)
+
+    def __repr__(self):
+        if self.alias_name:
+            return f"{self.default_name} AS {self.alias_name}"
+        return self.default_name
+
+
 def col(name: str) -> Col:
     return Col(name)
 

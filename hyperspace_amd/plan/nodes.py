@@ -1,8 +1,8 @@
 """Logical plan nodes.
 
 The engine's analog of Spark's LogicalPlan for the subset Hyperspace
-rewrites: file-source scans, filter, project, equi-join — plus the two
-rewrite-target nodes: IndexScan (reference IndexHadoopFsRelation,
+rewrites: file-source scans, filter, project, equi-join, aggregate — plus
+the two rewrite-target nodes: IndexScan (reference IndexHadoopFsRelation,
 index/plans/logical/IndexHadoopFsRelation.scala:29) and BucketUnionNode
 (reference BucketUnion, index/plans/logical/BucketUnion.scala:31).
 
@@ -15,7 +15,7 @@ from __future__ import annotations
 
 from typing import Any, Dict, List, Optional, Tuple
 
-from .expr import Expr
+from .expr import AggExpr, Expr
 from ..exceptions import HyperspaceException
 
 
@@ -180,6 +180,33 @@ class Join(LogicalPlan):
         if self.join_type == "inner":
             return f"Join({self.condition!r})"
         return f"Join({self.join_type}, {self.condition!r})"
+
+
+class Aggregate(LogicalPlan):
+    """Group ``child`` by ``group_cols`` and compute ``aggs`` per group;
+    no grouping columns = one global group, no aggregates = distinct.
+    Output: the grouping columns, then one column per aggregate."""
+
+    def __init__(self, group_cols: List[str], aggs: List[AggExpr],
+                 child: LogicalPlan):
+        super().__init__([child])
+        self.group_cols = list(group_cols)
+        self.aggs = list(aggs)
+
+    @property
+    def child(self):
+        return self.children[0]
+
+    def output_columns(self):
+        return self.group_cols + [a.output_name for a in self.aggs]
+
+    def with_children(self, children):
+        return Aggregate(self.group_cols, self.aggs, children[0])
+
+    def _node_str(self):
+        keys = ", ".join(self.group_cols)
+        aggs = ", ".join(repr(a) for a in self.aggs)
+        return f"Aggregate(keys=[{keys}], [{aggs}])"
 
 
 class IndexScan(LogicalPlan):

@@ -9,7 +9,7 @@ from __future__ import annotations
 
 from typing import Dict, List
 
-from ..plan.nodes import IndexScan, LogicalPlan
+from ..plan.nodes import Aggregate, IndexScan, LogicalPlan
 from ..rules.apply_hyperspace import ApplyHyperspace
 from ..rules.filter_reason import ReasonCollector
 
@@ -33,6 +33,11 @@ def _operator_counts(plan: LogicalPlan) -> Dict[str, int]:
     def walk(n):
         name = type(n).__name__
         counts[name] = counts.get(name, 0) + 1
+        if isinstance(n, Aggregate):
+            # the physical operator the aggregate runs as
+            from ..execution.executor import aggregate_operator_name
+            phys = aggregate_operator_name(n)
+            counts[phys] = counts.get(phys, 0) + 1
         for c in n.children:
             walk(c)
 

@@ -25,6 +25,7 @@ class FilterReasons:
     MISSING_INDEXED_COL = "MISSING_INDEXED_COL"
     ANOTHER_INDEX_APPLIED = "ANOTHER_INDEX_APPLIED"
     NO_FILTER_ON_INDEXED_COL = "NO_FILTER_ON_INDEXED_COL"
+    GROUP_COLS_NOT_INDEXED_COL = "GROUP_COLS_NOT_INDEXED_COL"
 
 
 @dataclass

@@ -1,4 +1,5 @@
-"""The rewrite rules: FilterIndexRule, JoinIndexRule, NoOpRule.
+"""The rewrite rules: FilterIndexRule, JoinIndexRule, AggregateIndexRule,
+NoOpRule.
 
 Reference:
   - HyperspaceRule template  index/rules/HyperspaceRule.scala:28-91
@@ -11,6 +12,11 @@ Reference:
   - JoinIndexRanker          index/covering/JoinIndexRanker.scala:52-90
   - FilterIndexRanker        index/covering/FilterIndexRanker.scala:43-64
   - plan surgery             index/covering/CoveringIndexRuleUtils.scala
+  - AggregateIndexRule has no rule of its own in the reference: Spark
+    drops the Exchange and Sort under an aggregate whose child's bucket
+    spec matches the grouping keys; here the rule exposes that layout
+    (single-column covering index == the grouping column; score = 70 ×
+    coverage, the per-side join score)
 """
 
 from __future__ import annotations
@@ -21,8 +27,8 @@ from .candidate_collector import (Candidate, TAG_APPENDED_FILES,
                                   TAG_DELETED_FILE_IDS)
 from .filter_reason import FilterReason, FilterReasons, ReasonCollector
 from ..plan.expr import extract_equi_join_keys
-from ..plan.nodes import (BucketUnionNode, Filter, IndexScan, Join,
-                          LogicalPlan, Project, Scan, UnionNode)
+from ..plan.nodes import (Aggregate, BucketUnionNode, Filter, IndexScan,
+                          Join, LogicalPlan, Project, Scan, UnionNode)
 
 
 class HyperspaceRule:
@@ -99,6 +105,36 @@ def _hybrid_appended_scan(cand: Candidate, scan: Scan,
                                  file_subset=appended))
 
 
+def _rewrite_bucketed_side(cand: Candidate, scan: Scan,
+                           proj: Optional[Project], filt: Optional[Filter],
+                           needed: List[str]) -> LogicalPlan:
+    """Project?-Filter?-Scan over the index's bucketed layout: a bucketed
+    IndexScan (lineage exclusion for deleted files), bucket-unioned with
+    the appended files under hybrid scan, the original Filter and Project
+    back on top.  Shared by the join and aggregate rules."""
+    index_scan = _index_scan_for(cand, needed, use_bucket_spec=True)
+    appended = _hybrid_appended_scan(cand, scan, needed)
+    if appended is not None:
+        node: LogicalPlan = BucketUnionNode(
+            [index_scan, appended], cand.index.num_buckets,
+            cand.index.indexed_columns)
+    else:
+        node = index_scan
+    if filt is not None:
+        node = Filter(filt.condition, node)
+    if proj is not None:
+        node = Project(proj.columns, node)
+    return node
+
+
+def _rank_by_size(cands: List[Candidate]) -> Candidate:
+    """Hybrid-scan era: max common bytes; else min index size
+    (reference: FilterIndexRanker.scala:43-64)."""
+    if any(c.hybrid_required for c in cands):
+        return max(cands, key=lambda c: c.common_bytes)
+    return min(cands, key=lambda c: c.entry.index_files_size())
+
+
 class FilterIndexRule(HyperspaceRule):
     name = "FilterIndexRule"
     SCORE = 50.0
@@ -150,11 +186,7 @@ class FilterIndexRule(HyperspaceRule):
         return new_plan, score
 
     def _rank(self, cands: List[Candidate]) -> Candidate:
-        """Hybrid-scan era: max common bytes; else min index size
-        (reference: FilterIndexRanker.scala:43-64)."""
-        if any(c.hybrid_required for c in cands):
-            return max(cands, key=lambda c: c.common_bytes)
-        return min(cands, key=lambda c: c.entry.index_files_size())
+        return _rank_by_size(cands)
 
     def _rewrite_scan(self, cand: Candidate, scan: Scan,
                       needed: List[str]) -> LogicalPlan:
@@ -293,16 +325,74 @@ class JoinIndexRule(HyperspaceRule):
     def _rewrite_side(self, cand: Candidate, scan: Scan,
                       proj: Optional[Project], filt: Optional[Filter],
                       needed: List[str]) -> LogicalPlan:
-        index_scan = _index_scan_for(cand, needed, use_bucket_spec=True)
-        appended = _hybrid_appended_scan(cand, scan, needed)
-        if appended is not None:
-            node: LogicalPlan = BucketUnionNode(
-                [index_scan, appended], cand.index.num_buckets,
-                cand.index.indexed_columns)
+        return _rewrite_bucketed_side(cand, scan, proj, filt, needed)
+
+
+class AggregateIndexRule(HyperspaceRule):
+    """Serve a single-column group-by from a covering index bucketed and
+    sorted on that column: every group lives in one bucket with its rows
+    adjacent, so the aggregate runs without exchange or sort.
+
+    Multi-column indexes are excluded on purpose: multi-file buckets and
+    bucket unions are re-sorted on the first indexed column only, so equal
+    tuples of a multi-column key are not guaranteed adjacent."""
+    name = "AggregateIndexRule"
+    SCORE = 70.0
+
+    def apply(self, plan, candidates):
+        if not isinstance(plan, Aggregate) or \
+                not self.session.conf.aggregate_rule_enabled:
+            return plan, 0.0
+        shape = _decompose_linear(plan.child)
+        if shape is None:
+            return plan, 0.0
+        project, filt, scan = shape
+        cands = candidates.get(id(scan), [])
+        if not cands:
+            return plan, 0.0
+        # what the child must deliver: a Project names it (plus the
+        # filter references); without one, only what the aggregate and
+        # the filter read, not the whole relation
+        if project is not None:
+            needed = _needed_columns(project, filt, scan)
         else:
-            node = index_scan
-        if filt is not None:
-            node = Filter(filt.condition, node)
-        if proj is not None:
-            node = Project(proj.columns, node)
-        return node
+            needed = list(plan.group_cols)
+            refs = set().union(*[a.references() for a in plan.aggs]) \
+                if plan.aggs else set()
+            if filt is not None:
+                refs |= filt.condition.references()
+            have = {c.lower() for c in needed}
+            for r in sorted(refs):
+                if r.lower() not in have:
+                    needed.append(r)
+                    have.add(r.lower())
+        group = [c.lower() for c in plan.group_cols]
+        eligible: List[Candidate] = []
+        for cand in cands:
+            index = cand.index
+            if index.kind != "CoveringIndex":
+                continue
+            if len(index.indexed_columns) != 1 or \
+                    [c.lower() for c in index.indexed_columns] != group:
+                self.reasons.add(cand.name, plan, FilterReason(
+                    FilterReasons.GROUP_COLS_NOT_INDEXED_COL,
+                    {"groupCols": str(plan.group_cols),
+                     "indexedCols": str(index.indexed_columns)}))
+                continue
+            covered = {c.lower() for c in index.referenced_columns()}
+            if not {c.lower() for c in needed} <= covered:
+                self.reasons.add(cand.name, plan, FilterReason(
+                    FilterReasons.MISSING_REQUIRED_COL,
+                    {"needed": str(needed)}))
+                continue
+            eligible.append(cand)
+        if not eligible:
+            return plan, 0.0
+        best = _rank_by_size(eligible)
+        child = _rewrite_bucketed_side(best, scan, project, filt, needed)
+        self.reasons.applied.setdefault(best.name, []).append(self.name)
+        from ..telemetry import HyperspaceIndexUsageEvent
+        self.session.event_logger.log_event(HyperspaceIndexUsageEvent(
+            index_names=[best.name], message="AggregateIndexRule applied"))
+        return (Aggregate(plan.group_cols, plan.aggs, child),
+                self.SCORE * _coverage(best))

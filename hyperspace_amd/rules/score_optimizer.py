@@ -12,8 +12,8 @@ from typing import Dict, List, Tuple
 
 from .candidate_collector import Candidate
 from .filter_reason import ReasonCollector
-from .hyperspace_rules import (FilterIndexRule, HyperspaceRule,
-                               JoinIndexRule, NoOpRule)
+from .hyperspace_rules import (AggregateIndexRule, FilterIndexRule,
+                               HyperspaceRule, JoinIndexRule, NoOpRule)
 from ..plan.nodes import LogicalPlan
 
 
@@ -24,6 +24,7 @@ class ScoreBasedIndexPlanOptimizer:
         self.rules: List[HyperspaceRule] = [
             FilterIndexRule(session, reasons),
             JoinIndexRule(session, reasons),
+            AggregateIndexRule(session, reasons),
         ]
         # secondary index kinds participate when present
         try:

@@ -27,6 +27,7 @@ setup(
             sources=[
                 "hyperspace_amd/csrc/binding.cpp",
                 "hyperspace_amd/csrc/kernels/kernels.hip",
+                "hyperspace_amd/csrc/kernels/aggregate.hip",
             ],
             include_dirs=[os.path.join(ROOT, "hyperspace_amd", "csrc")],
             extra_compile_args={
