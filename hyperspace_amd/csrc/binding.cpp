@@ -60,12 +60,16 @@ torch::Tensor murmur3_bucket(std::vector<torch::Tensor> keys,
     int kind;
     switch (col.scalar_type()) {
       case torch::kInt64:
-      case torch::kFloat64:
         kind = 1;
         break;
+      case torch::kFloat64:
+        kind = 3;  // hashed as canonical bits: -0.0 as 0.0, one NaN
+        break;
       case torch::kInt32:
-      case torch::kFloat32:
         kind = 0;
+        break;
+      case torch::kFloat32:
+        kind = 2;
         break;
       case torch::kInt16:
       case torch::kInt8:
@@ -100,7 +104,7 @@ torch::Tensor murmur3_bucket(std::vector<torch::Tensor> keys,
   return out;
 }
 
-torch::Tensor normalize_key(torch::Tensor vals) {
+torch::Tensor normalize_key(torch::Tensor vals, bool canonical = false) {
   check_cuda(vals, "vals");
   auto n = vals.numel();
   auto out = torch::empty(
@@ -108,7 +112,7 @@ torch::Tensor normalize_key(torch::Tensor vals) {
   hsk::normalize_key(vals.data_ptr(),
                      normalize_dtype_code(vals.scalar_type()),
                      (uint64_t*)out.data_ptr<int64_t>(), n,
-                     current_stream());
+                     current_stream(), canonical);
   return out;
 }
 
@@ -839,7 +843,8 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("murmur3_bucket", &murmur3_bucket, "Spark-compatible murmur3 bucket",
         py::arg("keys"), py::arg("num_buckets"),
         py::arg("masks") = std::vector<torch::Tensor>{});
-  m.def("normalize_key", &normalize_key, "order-preserving u64 key");
+  m.def("normalize_key", &normalize_key, "order-preserving u64 key",
+        py::arg("vals"), py::arg("canonical") = false);
   m.def("radix_sort_pairs", &radix_sort_pairs, "stable LSD radix sort");
   m.def("radix_sort_plan", &radix_sort_plan,
         "pass plan of the radix sort for a varying-bit mask: "

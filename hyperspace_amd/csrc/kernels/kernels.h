@@ -9,7 +9,9 @@
 namespace hsk {
 
 // K2: Spark-compatible Murmur3 fold over one column into h (u32 in u32 buf).
-// kind: 0 = i32-hash (int32 input), 1 = i64-hash (int64 input).
+// kind: 0 = i32-hash (int32 input), 1 = i64-hash (int64 input), 2 = float32
+// and 3 = float64 bits, hashed with -0.0 as +0.0 and every NaN as the
+// canonical quiet NaN (Java floatToIntBits / doubleToLongBits).
 // valid: optional per-row validity bytes — a null row leaves h unchanged
 // (Spark Murmur3Hash skips null children); nullptr = all valid.
 void murmur3_column(const void* vals, int kind, const uint8_t* valid,
@@ -19,9 +21,10 @@ void pmod_buckets(const uint32_t* h, int32_t* out, int64_t n,
                   int32_t num_buckets, hipStream_t stream);
 
 // order-preserving u64 normalization (dtype codes: 0=i64,1=i32,2=f64,3=f32,
-// 4=i16, 5=i8, 6=bool/u8)
+// 4=i16, 5=i8, 6=bool/u8).  canonical: float zeros and NaNs collapse first
+// (SQL equality: the key of -0.0 is that of +0.0, all NaNs share the top key)
 void normalize_key(const void* vals, int dtype, uint64_t* out, int64_t n,
-                   hipStream_t stream);
+                   hipStream_t stream, bool canonical = false);
 
 // K3: stable LSD radix sort of (u64 key, i64 payload), ascending u64 order.
 // keys/payload are sorted in place; tmp buffers same size provided by caller.

@@ -99,7 +99,21 @@ __device__ __forceinline__ uint32_t murmur_i64(uint64_t v, uint32_t seed) {
   return fmix(h1, 8);
 }
 
-template <typename T, bool IS64>
+// SQL equality for float keys: -0.0 hashes and compares as +0.0, and every
+// NaN as the one canonical quiet NaN (what Java's doubleToLongBits /
+// floatToIntBits give Spark).  Works on the raw bit pattern.
+__device__ __forceinline__ uint64_t canon_f64_bits(uint64_t b) {
+  if ((b & 0x7FFFFFFFFFFFFFFFull) > 0x7FF0000000000000ull)
+    return 0x7FF8000000000000ull;
+  return b == 0x8000000000000000ull ? 0ull : b;
+}
+
+__device__ __forceinline__ uint32_t canon_f32_bits(uint32_t b) {
+  if ((b & 0x7FFFFFFFu) > 0x7F800000u) return 0x7FC00000u;
+  return b == 0x80000000u ? 0u : b;
+}
+
+template <typename T, bool IS64, bool FLOAT>
 __global__ void k_murmur(const T* __restrict__ vals,
                          const uint8_t* __restrict__ valid,
                          uint32_t* __restrict__ h,
@@ -114,10 +128,13 @@ __global__ void k_murmur(const T* __restrict__ vals,
       h[i] = s;
       continue;
     }
-    if (IS64)
-      h[i] = murmur_i64((uint64_t)vals[i], s);
-    else
-      h[i] = murmur_i32((uint32_t)vals[i], s);
+    if (IS64) {
+      uint64_t v = (uint64_t)vals[i];
+      h[i] = murmur_i64(FLOAT ? canon_f64_bits(v) : v, s);
+    } else {
+      uint32_t v = (uint32_t)vals[i];
+      h[i] = murmur_i32(FLOAT ? canon_f32_bits(v) : v, s);
+    }
   }
 }
 
@@ -135,15 +152,24 @@ __global__ void k_pmod(const uint32_t* __restrict__ h,
 void murmur3_column(const void* vals, int kind, const uint8_t* valid,
                     uint32_t* h, int64_t n, bool first, uint32_t seed,
                     hipStream_t stream) {
+  // kind: 0 = 32-bit int, 1 = 64-bit int, 2 = float32, 3 = float64
   int g = grid_for(n);
   if (kind == 1) {
-    hipLaunchKernelGGL((k_murmur<uint64_t, true>), dim3(g), dim3(THREADS), 0,
-                       stream, (const uint64_t*)vals, valid, h, n, first,
-                       seed);
+    hipLaunchKernelGGL((k_murmur<uint64_t, true, false>), dim3(g),
+                       dim3(THREADS), 0, stream, (const uint64_t*)vals, valid,
+                       h, n, first, seed);
+  } else if (kind == 3) {
+    hipLaunchKernelGGL((k_murmur<uint64_t, true, true>), dim3(g),
+                       dim3(THREADS), 0, stream, (const uint64_t*)vals, valid,
+                       h, n, first, seed);
+  } else if (kind == 2) {
+    hipLaunchKernelGGL((k_murmur<uint32_t, false, true>), dim3(g),
+                       dim3(THREADS), 0, stream, (const uint32_t*)vals, valid,
+                       h, n, first, seed);
   } else {
-    hipLaunchKernelGGL((k_murmur<uint32_t, false>), dim3(g), dim3(THREADS), 0,
-                       stream, (const uint32_t*)vals, valid, h, n, first,
-                       seed);
+    hipLaunchKernelGGL((k_murmur<uint32_t, false, false>), dim3(g),
+                       dim3(THREADS), 0, stream, (const uint32_t*)vals, valid,
+                       h, n, first, seed);
   }
 }
 
@@ -172,23 +198,29 @@ __global__ void k_norm_small_int(const T* in, uint64_t* out, int64_t n) {
     out[i] = (uint64_t)(int64_t)in[i] ^ 0x8000000000000000ull;
 }
 
+// CANON: the SQL-equality key (ops.sql_key) — zeros and NaNs collapse as
+// in canon_f64_bits before the order-preserving flip, in the same pass.
+template <bool CANON>
 __global__ void k_norm_f64(const double* in, uint64_t* out, int64_t n) {
   int64_t stride = (int64_t)gridDim.x * blockDim.x;
   for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n;
        i += stride) {
     int64_t bits = __double_as_longlong(in[i]);
+    if (CANON) bits = (int64_t)canon_f64_bits((uint64_t)bits);
     uint64_t mask =
         bits < 0 ? 0xFFFFFFFFFFFFFFFFull : 0x8000000000000000ull;
     out[i] = (uint64_t)bits ^ mask;
   }
 }
 
+template <bool CANON>
 __global__ void k_norm_f32(const float* in, uint64_t* out, int64_t n) {
   int64_t stride = (int64_t)gridDim.x * blockDim.x;
   for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n;
        i += stride) {
     // match the CPU reference: widen to f64 first, then flip
     int64_t bits = __double_as_longlong((double)in[i]);
+    if (CANON) bits = (int64_t)canon_f64_bits((uint64_t)bits);
     uint64_t mask =
         bits < 0 ? 0xFFFFFFFFFFFFFFFFull : 0x8000000000000000ull;
     out[i] = (uint64_t)bits ^ mask;
@@ -196,7 +228,7 @@ __global__ void k_norm_f32(const float* in, uint64_t* out, int64_t n) {
 }
 
 void normalize_key(const void* vals, int dtype, uint64_t* out, int64_t n,
-                   hipStream_t stream) {
+                   hipStream_t stream, bool canonical) {
   int g = grid_for(n);
   switch (dtype) {
     case 0:
@@ -208,12 +240,20 @@ void normalize_key(const void* vals, int dtype, uint64_t* out, int64_t n,
                          stream, (const int32_t*)vals, out, n);
       break;
     case 2:
-      hipLaunchKernelGGL(k_norm_f64, dim3(g), dim3(THREADS), 0, stream,
-                         (const double*)vals, out, n);
+      if (canonical)
+        hipLaunchKernelGGL(k_norm_f64<true>, dim3(g), dim3(THREADS), 0,
+                           stream, (const double*)vals, out, n);
+      else
+        hipLaunchKernelGGL(k_norm_f64<false>, dim3(g), dim3(THREADS), 0,
+                           stream, (const double*)vals, out, n);
       break;
     case 3:
-      hipLaunchKernelGGL(k_norm_f32, dim3(g), dim3(THREADS), 0, stream,
-                         (const float*)vals, out, n);
+      if (canonical)
+        hipLaunchKernelGGL(k_norm_f32<true>, dim3(g), dim3(THREADS), 0,
+                           stream, (const float*)vals, out, n);
+      else
+        hipLaunchKernelGGL(k_norm_f32<false>, dim3(g), dim3(THREADS), 0,
+                           stream, (const float*)vals, out, n);
       break;
     case 4:
       hipLaunchKernelGGL(k_norm_small_int<int16_t>, dim3(g), dim3(THREADS), 0,

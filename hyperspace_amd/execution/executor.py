@@ -24,6 +24,7 @@ from typing import Dict, List, Optional, Tuple
 import torch
 
 from .columnar import ColumnBatch, StringColumn
+from . import sql_compare
 from .. import ops
 from ..config import IndexConstants
 from ..exceptions import HyperspaceException
@@ -289,7 +290,7 @@ class Executor:
                             files_per_bucket, file_ix_per_bucket):
                         if nfiles == 2:
                             split[b] = int(seg[b]) + row_counts[fi0]
-                    keys = ops.normalize_key(batch.tensor(sort_col))
+                    keys = ops.sql_key(batch.tensor(sort_col))
                     perm = ops.run_merge_perm(keys, seg, split)
                     batch = batch.gather(perm)
                 else:
@@ -300,7 +301,7 @@ class Executor:
                         sub = batch.slice(lo, hi)
                         if nfiles > 1 and sub.num_rows:
                             perm = ops.sort_perm(
-                                ops.normalize_key(sub.tensor(sort_col)))
+                                ops.sql_key(sub.tensor(sort_col)))
                             sub = sub.gather(perm)
                         pieces.append(sub)
                     batch = ColumnBatch.concat(pieces)
@@ -369,10 +370,14 @@ class Executor:
 
     def _bucket_of_value(self, index, col_name: str, value,
                          num_buckets: int) -> int:
+        """Bucket holding every row SQL-equal to the literal; -1 (no
+        bucket) when no value of the column's type equals it."""
         if index.schema.field_type(col_name) == "string":
             from ..ops.string_hash import bucket_of_string_value
             return bucket_of_string_value(str(value), num_buckets)
         t = _value_tensor(index.schema.field_type(col_name), value)
+        if t is None:
+            return -1
         return int(ops.cpu_ref.murmur3_bucket([t], num_buckets)[0])
 
     # ------------------------------------------------------------------
@@ -424,12 +429,16 @@ class Executor:
                            cond: Expr) -> torch.Tensor:
         """Native fast path for a single numeric comparison (select_range
         kernel); general path composes boolean masks."""
-        rng = _as_range(cond, batch)
-        if rng is not None and not any(
-                batch.has_column(c) and batch.has_nulls(c)
-                for c in cond.references()):
-            keys_u64, lo, hi, lo_incl, hi_incl = rng
-            return ops.select_range_u64(keys_u64, lo, hi, lo_incl, hi_incl)
+        if not any(batch.has_column(c) and batch.has_nulls(c)
+                   for c in cond.references()):
+            rng = _as_range(cond, batch)
+            if rng is not None:
+                col, lo, hi = rng
+                if lo is None:       # no value of the column can match
+                    return torch.empty(0, dtype=torch.int64,
+                                       device=batch.device)
+                return ops.select_range_u64(ops.sql_key(col), lo, hi,
+                                            True, True)
         mask = self._eval_mask(batch, cond)
         return torch.nonzero(mask, as_tuple=False).flatten()
 
@@ -476,10 +485,7 @@ class Executor:
         if isinstance(e, In):
             from ..plan.expr import Arith
             if isinstance(e.col, Arith):
-                t = _eval_arith(batch, e.col).to(torch.int64)
-                vs = torch.tensor(sorted(int(v) for v in e.values),
-                                  dtype=torch.int64, device=t.device)
-                m = ops.isin_sorted(t, vs)
+                m = _in_mask(_eval_arith(batch, e.col), e.values)
                 v = self._valid_of(batch, e)
                 return m & v if v is not None else m
             col = batch.column(e.col.name)
@@ -491,10 +497,7 @@ class Executor:
                     dtype=torch.int64, device=col.codes.device)
                 m = ops.isin_sorted(col.codes.to(torch.int64), codes)
             else:
-                t = col.to(torch.int64)
-                vs = torch.tensor(sorted(int(v) for v in vals),
-                                  dtype=torch.int64, device=t.device)
-                m = ops.isin_sorted(t, vs)
+                m = _in_mask(col, vals)
             v = self._valid_of(batch, e)
             return m & v if v is not None else m
         if isinstance(e, BinComp):
@@ -518,10 +521,17 @@ class Executor:
         lbatch, lseg = self._exec(plan.left)
         rbatch, rseg = self._exec(plan.right)
 
+        # two indexes are co-bucketed only if equal keys hash alike: an
+        # int64 key and a narrower one (or double and float) land in
+        # different buckets, so such a pair joins on the shuffled path
+        co_bucketed = left_bucketed and right_bucketed and all(
+            _same_hash_kind(lbatch.column(ln), rbatch.column(rn))
+            for ln, rn in pairs)
+
         if plan.join_type != "inner":
             return self._exec_typed_join(
                 plan.join_type, pairs, lbatch, lseg, rbatch, rseg,
-                left_bucketed and right_bucketed)
+                co_bucketed)
 
         # inner-join SQL semantics: null join keys never match — drop
         # them up front (bucketed layouts keep NULLS FIRST per bucket,
@@ -529,7 +539,7 @@ class Executor:
         lbatch, lseg = _drop_null_keys(lbatch, lkeys_names[0], lseg)
         rbatch, rseg = _drop_null_keys(rbatch, rkeys_names[0], rseg)
 
-        if (left_bucketed and right_bucketed and lseg is not None
+        if (co_bucketed and lseg is not None
                 and rseg is not None and lseg.numel() == rseg.numel()):
             # zero-shuffle co-bucketed sort-merge join (K4):
             # both sides already hash-partitioned into the same buckets and
@@ -538,8 +548,8 @@ class Executor:
             self.stats.record("SortMergeJoin(co-bucketed)")
             lk_t, rk_t = _join_key_tensors(lbatch, rbatch,
                                            lkeys_names[0], rkeys_names[0])
-            lk = ops.normalize_key(lk_t)
-            rk = ops.normalize_key(rk_t)
+            lk = ops.sql_key(lk_t)
+            rk = ops.sql_key(rk_t)
             lidx, ridx = ops.merge_join(lk, rk, lseg, rseg)
         else:
             # on-the-fly sort-merge join: shuffle-equivalent (counts as an
@@ -549,8 +559,8 @@ class Executor:
             self.stats.record("SortMergeJoin(shuffled)")
             lk_t, rk_t = _join_key_tensors(lbatch, rbatch,
                                            lkeys_names[0], rkeys_names[0])
-            lk = ops.normalize_key(lk_t)
-            rk = ops.normalize_key(rk_t)
+            lk = ops.sql_key(lk_t)
+            rk = ops.sql_key(rk_t)
             lperm = ops.sort_perm(lk)
             rperm = ops.sort_perm(rk)
             lbatch = lbatch.gather(lperm)
@@ -583,8 +593,8 @@ class Executor:
         lbatch, lseg, lnull = _split_null_keys(lbatch, lkey, lseg)
         rbatch, rseg, rnull = _split_null_keys(rbatch, rkey, rseg)
         lk_t, rk_t = _join_key_tensors(lbatch, rbatch, lkey, rkey)
-        lk = ops.normalize_key(lk_t)
-        rk = ops.normalize_key(rk_t)
+        lk = ops.sql_key(lk_t)
+        rk = ops.sql_key(rk_t)
         if (both_bucketed and lseg is not None and rseg is not None
                 and lseg.numel() == rseg.numel()):
             self.stats.merge_joins += 1
@@ -756,6 +766,7 @@ class Executor:
 # ---------------------------------------------------------------------------
 
 _SPARK_DTYPES = {"long": torch.int64, "integer": torch.int32,
+                 "short": torch.int16, "byte": torch.int8,
                  "double": torch.float64, "float": torch.float32}
 
 
@@ -779,7 +790,15 @@ def _join_key_tensors(lbatch: ColumnBatch, rbatch: ColumnBatch,
         raise HyperspaceException(
             f"join key type mismatch: {ln} vs {rn}")
     if not lstr:
-        return lbatch.tensor(ln), rbatch.tensor(rn)
+        lt, rt = lbatch.tensor(ln), rbatch.tensor(rn)
+        if lt.dtype.is_floating_point != rt.dtype.is_floating_point:
+            # the u64 keys of an integer and of a float are unrelated:
+            # comparing them would silently match nothing
+            raise HyperspaceException(
+                f"join key type mismatch: {ln} ({lt.dtype}) vs {rn} "
+                f"({rt.dtype}): an integer key does not join a float "
+                "key, store both sides as one type")
+        return lt, rt
     merged = sorted(set(lcol.values) | set(rcol.values))
     vi = {v: i for i, v in enumerate(merged)}
     llut = torch.tensor([vi[v] for v in lcol.values], dtype=torch.int64,
@@ -838,7 +857,11 @@ def _secondary_key_filter(lbatch: ColumnBatch, rbatch: ColumnBatch, pairs,
                           device=lidx.device)
         for ln, rn in pairs[1:]:
             lv_t, rv_t = _join_key_tensors(lbatch, rbatch, ln, rn)
-            keep &= (lv_t[lidx] == rv_t[ridx])
+            lv, rv = lv_t[lidx], rv_t[ridx]
+            if lv.dtype.is_floating_point or lv.dtype != rv.dtype:
+                # SQL equality (-0.0 = 0.0, NaN = NaN), widths promoted
+                lv, rv = ops.sql_key(lv), ops.sql_key(rv)
+            keep &= (lv == rv)
             lm, rm = lbatch.mask(ln), rbatch.mask(rn)
             if lm is not None:
                 keep &= lm[lidx]
@@ -1092,6 +1115,9 @@ def _compare(batch: ColumnBatch, e: BinComp) -> torch.Tensor:
         lv = _eval_arith(batch, e.left)
         rv = (_eval_arith(batch, e.right)
               if not isinstance(e.right, Lit) else e.right.value)
+        if torch.is_tensor(lv) and isinstance(e.right, Lit) and \
+                sql_compare.supported(lv.dtype, rv):
+            return sql_compare.literal_mask(lv, e.op, rv)
         return {"=": lv == rv, "!=": lv != rv, "<": lv < rv,
                 "<=": lv <= rv, ">": lv > rv, ">=": lv >= rv}[e.op]
     if not isinstance(e.left, Col):
@@ -1125,6 +1151,8 @@ def _compare(batch: ColumnBatch, e: BinComp) -> torch.Tensor:
             if op == ">":
                 return codes >= pos + (1 if exact else 0)
             return codes >= pos  # >=
+        elif sql_compare.supported(col.dtype, value):
+            return sql_compare.literal_mask(col, e.op, value)
         else:
             lv = col
             rv = torch.tensor(value, dtype=col.dtype, device=col.device)
@@ -1142,11 +1170,38 @@ def _compare(batch: ColumnBatch, e: BinComp) -> torch.Tensor:
     return lv >= rv
 
 
-def _value_tensor(spark_type: Optional[str], value) -> torch.Tensor:
+def _value_tensor(spark_type: Optional[str], value
+                  ) -> Optional[torch.Tensor]:
+    """The literal as a one-element tensor of the column's type, for
+    hashing to its bucket; None when no value of that type equals it."""
     dt = _SPARK_DTYPES.get(spark_type or "", None)
     if dt is None:
         dt = torch.int64 if isinstance(value, int) else torch.float64
+    if sql_compare.supported(dt, value):
+        return sql_compare.equality_probe(dt, value)
     return torch.tensor([value], dtype=dt)
+
+
+def _in_mask(t: torch.Tensor, values) -> torch.Tensor:
+    """``t IN (values)`` for a numeric tensor: the OR of SQL ``=``."""
+    if all(sql_compare.supported(t.dtype, v) for v in values):
+        return sql_compare.in_mask(t, values)
+    vs = torch.tensor(sorted(int(v) for v in values), dtype=torch.int64,
+                      device=t.device)
+    return ops.isin_sorted(t.to(torch.int64), vs)
+
+
+def _same_hash_kind(lcol, rcol) -> bool:
+    """True if SQL-equal values of the two key columns hash to the same
+    bucket: murmur3 folds 64-bit integers, narrower integers, doubles
+    and floats each their own way."""
+    def kind(c):
+        if isinstance(c, StringColumn):
+            return "string"
+        if c.dtype.is_floating_point or c.dtype == torch.int64:
+            return c.dtype
+        return torch.int32
+    return kind(lcol) == kind(rcol)
 
 
 def _single_equality(cond: Expr) -> Optional[Tuple[str, object]]:
@@ -1158,36 +1213,27 @@ def _single_equality(cond: Expr) -> Optional[Tuple[str, object]]:
 
 def _as_range(cond: Expr, batch: ColumnBatch):
     """Lower a single numeric comparison to the select_range_u64 kernel:
-    returns (keys_u64, lo, hi, lo_incl, hi_incl) or None."""
+    returns (column, lo, hi) — closed u64 bounds over ``ops.sql_key`` of
+    the column, both None when nothing can match — or None when the
+    comparison takes the mask path."""
     if not (isinstance(cond, BinComp) and isinstance(cond.left, Col)
             and isinstance(cond.right, Lit)):
         return None
     col = batch.column(cond.left.name)
     if isinstance(col, StringColumn):
         return None
-    if col.dtype not in (torch.int8, torch.int16, torch.int32, torch.int64,
-                         torch.float32, torch.float64):
-        return None
     value = cond.right.value
-    vt = torch.tensor([value], dtype=col.dtype)
-    v = int(ops.cpu_ref.normalize_key(vt)[0])
-    keys = ops.normalize_key(col)
-    # u64-order sentinels in the int64-encoded u64 space:
-    # u64 0 encodes as int64 0; u64 max (0xFFFF..FF) encodes as int64 -1
-    UMIN = 0
-    UMAX = -1
-    op = cond.op
-    if op == "=":
-        return keys, v, v, True, True
-    if op == "<":
-        return keys, UMIN, v, True, False
-    if op == "<=":
-        return keys, UMIN, v, True, True
-    if op == ">":
-        return keys, v, UMAX, False, True
-    if op == ">=":
-        return keys, v, UMAX, True, True
-    return None
+    if not sql_compare.supported(col.dtype, value):
+        return None
+    spec = sql_compare.lower(col.dtype, cond.op, value)
+    if spec is sql_compare.NONE:
+        return col, None, None
+    if spec is sql_compare.ALL:
+        spec = ("range", sql_compare.S_MIN, sql_compare.S_MAX)
+    if spec[0] != "range":
+        return None
+    # s-space -> the int64-encoded u64 the kernel compares
+    return col, spec[1] ^ sql_compare.SIGN, spec[2] ^ sql_compare.SIGN
 
 
 def _bucketed_side(plan: LogicalPlan, key_names: List[str]) -> bool:

@@ -423,12 +423,14 @@ def _multi_key_sort_perm(batch: ColumnBatch, key_cols: List[str]
     (least-significant column first).  Nullable columns order ASC NULLS
     FIRST (Spark's default): a stable partition moves this column's null
     rows ahead after its key sort, giving (null-flag, key) lexicographic
-    order per column."""
+    order per column.  Float columns sort by their SQL key (-0.0 with
+    +0.0, every NaN last): that is the key the merge join compares, so
+    a bucket sorted by raw bits would not be sorted for it."""
     n = batch.num_rows
     dev = batch.device
     perm = torch.arange(n, dtype=torch.int64, device=dev)
     for c in reversed(key_cols):
-        keys = ops.normalize_key(batch.tensor(c))[perm]
+        keys = ops.sql_key(batch.tensor(c))[perm]
         _, perm = ops.sort_pairs(keys, perm)
         m = batch.mask(c)
         if m is not None and not bool(m.all()):

@@ -32,7 +32,7 @@ from . import cpu_ref, native
 from .cpu_ref import MASK32, SPARK_HASH_SEED  # re-export
 
 __all__ = [
-    "murmur3_bucket", "normalize_key", "sort_pairs", "sort_perm",
+    "murmur3_bucket", "normalize_key", "sql_key", "sort_pairs", "sort_perm",
     "merge_join", "run_merge_perm", "select_range_u64", "isin_sorted", "segmented_minmax",
     "bloom_build", "bloom_probe", "bloom_probe_many", "zorder_key", "gather_rows", "native",
     "group_offsets", "segmented_reduce", "group_tile_size",
@@ -43,6 +43,15 @@ def normalize_key(col: torch.Tensor) -> torch.Tensor:
     if col.is_cuda:
         return native.ext().normalize_key(col.contiguous())
     return cpu_ref.normalize_key(col)
+
+
+def sql_key(col: torch.Tensor) -> torch.Tensor:
+    """normalize_key under SQL equality: -0.0 keys as +0.0 and every NaN
+    as one key above +inf (same single kernel pass; integers unchanged).
+    Filters, join keys and the index build sort compare these."""
+    if col.is_cuda:
+        return native.ext().normalize_key(col.contiguous(), True)
+    return cpu_ref.sql_key(col)
 
 
 def gather_rows(values: torch.Tensor, idx: torch.Tensor) -> torch.Tensor:
@@ -59,7 +68,8 @@ def _is_cuda(*tensors: torch.Tensor) -> bool:
 def murmur3_bucket(keys: List[torch.Tensor], num_buckets: int,
                    masks=None) -> torch.Tensor:
     """masks: optional list parallel to keys; entries are bool validity
-    tensors or None (no nulls in that key column)."""
+    tensors or None (no nulls in that key column).  Float keys hash
+    their canonical bits: -0.0 as +0.0, every NaN as the quiet NaN."""
     if _is_cuda(*keys):
         if masks is not None and any(m is not None for m in masks):
             mlist = [

@@ -76,17 +76,19 @@ def murmur3_bucket(keys: List[torch.Tensor], num_buckets: int,
     h = seed 42 folded over columns, bucket = pmod(h, n).  A null key
     column leaves the running hash unchanged (Murmur3Hash skips null
     children, so an all-null single-key row lands in pmod(42, n)).
+    Float keys hash their canonical bits (-0.0 as +0.0, one NaN), so
+    SQL-equal keys share a bucket.
     ``masks[i]`` is a bool validity tensor or None.  Returns int32."""
     h: Optional[torch.Tensor] = None
     for ci, k in enumerate(keys):
         seed = SPARK_HASH_SEED if h is None else h
         if k.dtype in (torch.int64, torch.float64):
             if k.dtype == torch.float64:
-                k = k.view(torch.int64)
+                k = canonical_float_bits(k)
             nh = murmur3_hash_int64(k, seed)
         else:
             if k.dtype == torch.float32:
-                k = k.view(torch.int32)
+                k = canonical_float_bits(k)
             nh = murmur3_hash_int32(k, seed)
         mask = masks[ci] if masks is not None else None
         if mask is not None and mask.numel():
@@ -120,6 +122,37 @@ def normalize_key(col: torch.Tensor) -> torch.Tensor:
     if col.dtype == torch.bool:
         return col.to(torch.int64) ^ (-0x8000000000000000)
     raise ValueError(f"Unsupported dtype for sort key: {col.dtype}")
+
+
+def canonical_float_bits(col: torch.Tensor) -> torch.Tensor:
+    """Bit pattern (int64 / int32) of a float64 / float32 column under SQL
+    equality: -0.0 becomes +0.0 and every NaN, whatever its sign or
+    payload, the canonical quiet NaN 0x7ff8000000000000 / 0x7fc00000 —
+    what Java's doubleToLongBits / floatToIntBits hand to Spark's hash."""
+    if col.dtype == torch.float64:
+        bits = col.contiguous().view(torch.int64)
+        mag, inf, nan = 0x7FFFFFFFFFFFFFFF, 0x7FF0000000000000, \
+            0x7FF8000000000000
+        neg_zero = -0x8000000000000000
+    elif col.dtype == torch.float32:
+        bits = col.contiguous().view(torch.int32)
+        mag, inf, nan, neg_zero = 0x7FFFFFFF, 0x7F800000, 0x7FC00000, \
+            -0x80000000
+    else:
+        raise ValueError(f"not a float column: {col.dtype}")
+    bits = torch.where((bits & mag) > inf, torch.full_like(bits, nan), bits)
+    return torch.where(bits == neg_zero, torch.zeros_like(bits), bits)
+
+
+def sql_key(col: torch.Tensor) -> torch.Tensor:
+    """``normalize_key`` under SQL equality and ordering: equal keys <=>
+    SQL-equal values.  Float zeros share one key and all NaNs share the
+    largest one (above +inf); integer columns are unchanged."""
+    if col.dtype == torch.float32:
+        col = col.to(torch.float64)
+    if col.dtype == torch.float64:
+        col = canonical_float_bits(col).view(torch.float64)
+    return normalize_key(col)
 
 
 def _as_unsigned_sortable(u64: torch.Tensor) -> torch.Tensor:

@@ -46,6 +46,19 @@ def test_murmur3_multi_column_fold():
     assert not torch.equal(b1, b3)  # order matters
 
 
+def test_murmur3_float_keys_hash_canonical_bits():
+    """-0.0 hashes as +0.0 and every NaN as the canonical NaN (what
+    Java's doubleToLongBits / floatToIntBits give Spark's hash): both
+    float widths, single and folded, with and without a mask."""
+    import sql_semantics_common as sc
+    sc.check_float_hash_pins(cpu_ref.murmur3_bucket)
+
+
+def test_sql_key_is_the_canonical_normalize_key():
+    import sql_semantics_common as sc
+    sc.check_sql_key_pins(cpu_ref.sql_key, cpu_ref.normalize_key)
+
+
 def test_normalize_key_order_preserving():
     for dtype in (torch.int64, torch.int32, torch.float64, torch.float32):
         if dtype.is_floating_point:

@@ -46,6 +46,43 @@ def test_murmur3_bucket_multi_col():
     assert torch.equal(cpu, gpu)
 
 
+def _on_gpu(fn):
+    def run(keys, nb, masks):
+        return fn([k.cuda() for k in keys], nb,
+                  None if masks is None else
+                  [None if m is None else m.cuda() for m in masks]).cpu()
+    return run
+
+
+def test_murmur3_float_keys_hash_canonical_bits():
+    """k_murmur's float kinds: -0.0 hashes as +0.0, every NaN as the
+    canonical NaN — pinned in plain Python, and equal to cpu_ref at the
+    block edges (n = 1, 255, 256, 257, 1,025)."""
+    import sql_semantics_common as sc
+    sc.check_float_hash_pins(_on_gpu(ops.murmur3_bucket))
+    for width in (64, 32):
+        for n in sc.EDGE_SIZES:
+            f, _ = sc.float_key_column(width, n)
+            lead = torch.arange(n, dtype=torch.int32)
+            mask = torch.arange(n) % 3 != 1
+            for keys, masks in (([f], None), ([f], [mask]),
+                                ([lead, f], [None, mask])):
+                assert torch.equal(
+                    cpu_ref.murmur3_bucket(keys, 200, masks),
+                    _on_gpu(ops.murmur3_bucket)(keys, 200, masks)), (width, n)
+
+
+def test_sql_key_matches_cpu_and_canonical_bits():
+    import sql_semantics_common as sc
+    sc.check_sql_key_pins(lambda t: ops.sql_key(t.cuda()).cpu(),
+                          lambda t: ops.normalize_key(t.cuda()).cpu())
+    for width in (64, 32):
+        for n in sc.EDGE_SIZES:
+            f, _ = sc.float_key_column(width, n)
+            assert torch.equal(cpu_ref.sql_key(f),
+                               ops.sql_key(f.cuda()).cpu()), (width, n)
+
+
 def test_normalize_key_matches_cpu():
     for dtype in (torch.int64, torch.int32, torch.float64, torch.float32):
         if dtype.is_floating_point:
