@@ -49,7 +49,12 @@ torch::Tensor murmur3_bucket(std::vector<torch::Tensor> keys,
               num_buckets);
   auto n = keys[0].numel();
   auto dev = keys[0].device();
-  auto h = torch::empty({n}, torch::dtype(torch::kInt32).device(dev));
+  // the running hash reaches HBM only between columns: the last column's
+  // kernel applies the pmod to the hash in its register
+  torch::Tensor h;
+  if (keys.size() > 1)
+    h = torch::empty({n}, torch::dtype(torch::kInt32).device(dev));
+  auto out = torch::empty({n}, torch::dtype(torch::kInt32).device(dev));
   auto stream = current_stream();
   bool first = true;
   for (size_t ci = 0; ci < keys.size(); ++ci) {
@@ -92,15 +97,17 @@ torch::Tensor murmur3_bucket(std::vector<torch::Tensor> keys,
                   "mask must be bool/uint8");
       valid = (const uint8_t*)mcol.data_ptr();
     }
-    hsk::murmur3_column(col.data_ptr(), kind, valid,
-                        (uint32_t*)h.data_ptr<int32_t>(), n, first,
-                        /*seed=*/42u, stream);
+    uint32_t* hp =
+        h.defined() ? (uint32_t*)h.data_ptr<int32_t>() : nullptr;
+    if (ci + 1 < keys.size())
+      hsk::murmur3_column(col.data_ptr(), kind, valid, hp, n, first,
+                          /*seed=*/42u, stream);
+    else
+      hsk::murmur3_last_column(col.data_ptr(), kind, valid, hp,
+                               out.data_ptr<int32_t>(), n, first,
+                               /*seed=*/42u, (int32_t)num_buckets, stream);
     first = false;
   }
-  auto out = torch::empty({n}, torch::dtype(torch::kInt32).device(dev));
-  hsk::pmod_buckets((const uint32_t*)h.data_ptr<int32_t>(),
-                    out.data_ptr<int32_t>(), n, (int32_t)num_buckets,
-                    stream);
   return out;
 }
 
@@ -677,11 +684,90 @@ void copy_unaligned(torch::Tensor src_u8, int64_t src_off,
 torch::Tensor gather_rows(torch::Tensor values, torch::Tensor idx) {
   check_cuda(values, "values");
   check_cuda(idx, "idx");
-  TORCH_CHECK(idx.scalar_type() == torch::kInt64, "idx must be int64");
+  TORCH_CHECK(idx.scalar_type() == torch::kInt64 ||
+                  idx.scalar_type() == torch::kInt32,
+              "idx must be int64 or int32");
   auto out = torch::empty({idx.numel()}, values.options());
-  hsk::gather(values.data_ptr(), idx.data_ptr<int64_t>(), out.data_ptr(),
-              idx.numel(), (int)values.element_size(), current_stream());
+  if (idx.scalar_type() == torch::kInt32)
+    hsk::gather(values.data_ptr(), idx.data_ptr<int32_t>(), out.data_ptr(),
+                idx.numel(), (int)values.element_size(), current_stream());
+  else
+    hsk::gather(values.data_ptr(), idx.data_ptr<int64_t>(), out.data_ptr(),
+                idx.numel(), (int)values.element_size(), current_stream());
   return out;
+}
+
+int bit_length_u64(uint64_t v) { return v ? 64 - __builtin_clzll(v) : 0; }
+
+// Fused (bucket, key) sort for one non-null integer key column: returns
+// (perm int32, key column in sorted order, seg int64 on the CPU), or None
+// when the key range does not fit beside the bucket bits.  bucket_ids:
+// int32 in [0, num_buckets).  The composite (bucket << S) | (key - kmin)
+// is sorted once with a generated row-index payload; seg and the sorted
+// key column are read back off the sorted composite.
+py::object bucket_sort_perm(torch::Tensor key, torch::Tensor bucket_ids,
+                            int64_t num_buckets) {
+  check_cuda(key, "key");
+  check_cuda(bucket_ids, "bucket_ids");
+  TORCH_CHECK(bucket_ids.scalar_type() == torch::kInt32,
+              "bucket_ids must be int32");
+  TORCH_CHECK(num_buckets > 0 && num_buckets <= (int64_t)INT32_MAX,
+              "bucket_sort_perm: num_buckets must be in 1..INT32_MAX, got ",
+              num_buckets);
+  int dtype = normalize_dtype_code(key.scalar_type());
+  TORCH_CHECK(dtype != 2 && dtype != 3,
+              "bucket_sort_perm: integer keys only");
+  int64_t n = key.numel();
+  TORCH_CHECK(bucket_ids.numel() == n, "bucket_ids length mismatch");
+  if (n <= 1 || n > (int64_t)INT32_MAX) return py::none();
+  auto dev = key.device();
+  auto i64 = torch::dtype(torch::kInt64).device(dev);
+  auto i32 = torch::dtype(torch::kInt32).device(dev);
+  auto stream = current_stream();
+
+  auto mm = torch::empty({2}, i64);
+  hsk::key_minmax(key.data_ptr(), dtype, n,
+                  (uint64_t*)mm.data_ptr<int64_t>(), stream);
+  auto mm_host = mm.cpu();
+  uint64_t kmin = (uint64_t)mm_host.data_ptr<int64_t>()[0];
+  uint64_t range = (uint64_t)mm_host.data_ptr<int64_t>()[1] - kmin;
+  int bbits = bit_length_u64((uint64_t)num_buckets - 1);
+  int kbits = bit_length_u64(range);
+  if (kbits + bbits > 64) return py::none();
+  // the bucket field starts on a byte boundary so that it shares no
+  // radix digit with the key, unless only the tight layout fits 64 bits
+  int shift = (kbits + 7) / 8 * 8;
+  if (shift + bbits > 64) shift = 64 - bbits;
+  uint64_t low_mask = kbits ? ~0ull >> (64 - kbits) : 0;
+  // varying bits, from the ranges alone: no reduce over the composite
+  uint64_t mask = low_mask;
+  if (bbits) mask |= (~0ull >> (64 - bbits)) << shift;
+
+  auto comp = torch::empty({n}, i64);
+  auto tmp_comp = torch::empty({n}, i64);
+  auto perm = torch::empty({n}, i32);
+  auto tmp_perm = torch::empty({n}, i32);
+  auto hist = torch::empty({hsk::radix_sort_hist_size(n)}, i32);
+  hsk::compose_bucket_key(key.data_ptr(), dtype,
+                          bucket_ids.data_ptr<int32_t>(), kmin, shift,
+                          (uint64_t*)comp.data_ptr<int64_t>(), n, stream);
+  if (hsk::radix_sort_index32((uint64_t*)comp.data_ptr<int64_t>(),
+                              perm.data_ptr<int32_t>(),
+                              (uint64_t*)tmp_comp.data_ptr<int64_t>(),
+                              tmp_perm.data_ptr<int32_t>(),
+                              (uint32_t*)hist.data_ptr<int32_t>(), mask, n,
+                              stream)) {
+    std::swap(comp, tmp_comp);
+    std::swap(perm, tmp_perm);
+  }
+  auto sorted = (const uint64_t*)comp.data_ptr<int64_t>();
+  auto seg = torch::empty({num_buckets + 1}, i64);
+  hsk::bucket_seg_offsets(sorted, n, shift, (int32_t)num_buckets,
+                          seg.data_ptr<int64_t>(), stream);
+  auto sorted_key = torch::empty_like(key);
+  hsk::restore_key(sorted, low_mask, kmin, dtype, sorted_key.data_ptr(), n,
+                   stream);
+  return py::make_tuple(perm, sorted_key, seg.cpu());
 }
 
 // The group-by kernels read 16-byte vectors: a contiguous view that
@@ -862,7 +948,11 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("bloom_probe_many", &bloom_probe_many,
         "K9 device sketch-predicate probe over per-file filters");
   m.def("zorder_key", &zorder_key, "z-order bit interleave");
-  m.def("gather_rows", &gather_rows, "row gather by index");
+  m.def("gather_rows", &gather_rows,
+        "row gather by an int64 or int32 index");
+  m.def("bucket_sort_perm", &bucket_sort_perm,
+        "fused (bucket, integer key) sort: (perm int32, sorted key column, "
+        "seg) or None when the key range is too wide");
   m.def("copy_unaligned", &copy_unaligned,
         "device parquet page decode (unaligned copy)");
   m.def("run_merge_perm", &run_merge_perm,

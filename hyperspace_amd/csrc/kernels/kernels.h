@@ -17,8 +17,13 @@ namespace hsk {
 void murmur3_column(const void* vals, int kind, const uint8_t* valid,
                     uint32_t* h, int64_t n, bool first, uint32_t seed,
                     hipStream_t stream);
-void pmod_buckets(const uint32_t* h, int32_t* out, int64_t n,
-                  int32_t num_buckets, hipStream_t stream);
+// The fold over the LAST key column with the pmod applied in the same
+// kernel: out[i] = pmod(fold(h[i] or seed, vals[i]), num_buckets).  h is
+// only read, and may be null when first (a single key column).
+void murmur3_last_column(const void* vals, int kind, const uint8_t* valid,
+                         const uint32_t* h, int32_t* out, int64_t n,
+                         bool first, uint32_t seed, int32_t num_buckets,
+                         hipStream_t stream);
 
 // order-preserving u64 normalization (dtype codes: 0=i64,1=i32,2=f64,3=f32,
 // 4=i16, 5=i8, 6=bool/u8).  canonical: float zeros and NaNs collapse first
@@ -35,12 +40,41 @@ void radix_sort_pairs32(uint64_t* keys, int32_t* payload,
                         uint64_t* tmp_keys, int32_t* tmp_payload,
                         uint32_t* hist, uint64_t* d_mask, int64_t n,
                         hipStream_t stream);
+// Stable sort of u64 keys that returns the sorting permutation: the first
+// pass generates the payload as the row index, so perm/tmp_perm are only
+// buffers.  mask is a superset of the varying key bits, given by the
+// caller (no device reduce, no sync).  Nothing is copied back: returns
+// true when the result is in (tmp_keys, tmp_perm), false when it is in
+// (keys, perm).  1 <= n < 2^31.
+bool radix_sort_index32(uint64_t* keys, int32_t* perm, uint64_t* tmp_keys,
+                        int32_t* tmp_perm, uint32_t* hist, uint64_t mask,
+                        int64_t n, hipStream_t stream);
 // histogram buffer size requirement (u32 elements)
 int64_t radix_sort_hist_size(int64_t n);
 // pass plan the sort runs for a varying-bit mask (OR of key ^ key[0]):
 // returns the radix (256, or 512 when HS_RS_9BIT=1 and 9-bit digits save
 // a pass) and fills shifts[0..*npass) with the digit shifts, ascending.
 int radix_sort_plan(uint64_t mask, int shifts[8], int* npass);
+
+// Fused (bucket, key) sort of the index build, for one integer key column
+// (normalize_key dtype codes 0, 1, 4, 5, 6).  The sort key is the
+// composite (bucket << shift) | (normalized key - kmin).
+// key_minmax: mm[0] = min, mm[1] = max of the normalized keys (device).
+void key_minmax(const void* vals, int dtype, int64_t n, uint64_t* mm,
+                hipStream_t stream);
+// bucket ids must lie in [0, 2^(64 - shift)); shift == 64 needs all zero
+void compose_bucket_key(const void* vals, int dtype, const int32_t* buckets,
+                        uint64_t kmin, int shift, uint64_t* out, int64_t n,
+                        hipStream_t stream);
+// the key column of the sorted rows, from the sorted composite:
+// ((c & low_mask) + kmin) un-normalized, cast to the column's dtype
+void restore_key(const uint64_t* sorted, uint64_t low_mask, uint64_t kmin,
+                 int dtype, void* out, int64_t n, hipStream_t stream);
+// seg[b] = lower bound of (b << shift) in the sorted composite for
+// b < num_buckets, seg[num_buckets] = n (num_buckets + 1 entries)
+void bucket_seg_offsets(const uint64_t* sorted, int64_t n, int shift,
+                        int32_t num_buckets, int64_t* seg,
+                        hipStream_t stream);
 
 // K4: segmented sorted merge join, two-phase per-tile form.  Phase 1
 // writes one pair-count per 256-row left tile; after an exclusive scan
@@ -162,8 +196,11 @@ void bloom_probe_many(const int64_t* vals, int64_t n_vals,
 void zorder_key(const uint64_t* const* cols, int n_cols, int bits_per_col,
                 int64_t n, uint64_t* out, hipStream_t stream);
 
-// row gather: out[i] = in[idx[i]] for element sizes 4/8
+// row gather: out[i] = in[idx[i]] for element sizes 1/2/4/8, through an
+// int64 or an int32 index
 void gather(const void* in, const int64_t* idx, void* out, int64_t n,
+            int elem_size, hipStream_t stream);
+void gather(const void* in, const int32_t* idx, void* out, int64_t n,
             int elem_size, hipStream_t stream);
 
 // K1 parquet dictionary-page decode: expand an RLE/bit-packed hybrid

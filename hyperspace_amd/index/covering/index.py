@@ -461,11 +461,45 @@ def _bucket_seg_offsets(sorted_bkeys_u64: torch.Tensor, num_buckets: int
     return torch.searchsorted(sortable, sortable_probes).cpu()
 
 
+def _fused_bucket_sort(batch: ColumnBatch, bucket_ids: torch.Tensor,
+                       key_cols: List[str], num_buckets: int
+                       ) -> Optional[Tuple[ColumnBatch, torch.Tensor]]:
+    """The common index shape — one integer key column without nulls, on
+    the device — sorted by ops.bucket_sort_perm: one composite sort, the
+    key column rebuilt from it and every other column gathered once
+    through the int32 permutation.  None = not that shape, the caller
+    runs the general path.  HS_FUSED_BUCKET_SORT=0 (read per call) turns
+    it off."""
+    if len(key_cols) != 1 or os.environ.get("HS_FUSED_BUCKET_SORT") == "0":
+        return None
+    key_name = batch._stored_key(key_cols[0])
+    key = batch.columns[key_name]
+    if isinstance(key, StringColumn) or batch.has_nulls(key_name):
+        return None
+    res = ops.bucket_sort_perm(key, bucket_ids, num_buckets)
+    if res is None:
+        return None
+    perm, sorted_key, seg = res
+    cols: Dict[str, Any] = {}
+    for k, v in batch.columns.items():
+        if k == key_name:
+            cols[k] = sorted_key
+        elif isinstance(v, StringColumn):
+            cols[k] = StringColumn(ops.gather_rows(v.codes, perm), v.values)
+        else:
+            cols[k] = ops.gather_rows(v, perm)
+    return ColumnBatch(
+        cols, {k: m[perm] for k, m in batch.masks.items()}), seg
+
+
 def sort_by_bucket_and_keys(batch: ColumnBatch, bucket_ids: torch.Tensor,
                             key_cols: List[str], num_buckets: int
                             ) -> Tuple[ColumnBatch, torch.Tensor]:
     """Stable sort rows by (bucket, key columns); returns the reordered
     batch and per-bucket segment offsets (num_buckets+1)."""
+    fused = _fused_bucket_sort(batch, bucket_ids, key_cols, num_buckets)
+    if fused is not None:
+        return fused
     perm = _multi_key_sort_perm(batch, key_cols)
     b64 = ops.gather_rows(bucket_ids.to(torch.int64), perm)
     sorted_bkeys, perm2 = ops.sort_pairs(ops.normalize_key(b64), perm)

@@ -9,6 +9,7 @@ Op -> reference data-plane mapping:
   murmur3_bucket   K2  hash partitioning (Spark HashPartitioning-compatible,
                        null keys pass the seed through)
   sort_pairs       K3  per-bucket sort (stable LSD radix on device)
+  bucket_sort_perm K3  fused (bucket, integer key) sort of the index build
   merge_join       K4  co-bucketed sort-merge join (two-phase per-tile)
   run_merge_perm   K4b segmented two-sorted-run merge (multi-file buckets)
   select_range     K1/filter scan predicate + compaction
@@ -36,6 +37,7 @@ __all__ = [
     "merge_join", "run_merge_perm", "select_range_u64", "isin_sorted", "segmented_minmax",
     "bloom_build", "bloom_probe", "bloom_probe_many", "zorder_key", "gather_rows", "native",
     "group_offsets", "segmented_reduce", "group_tile_size",
+    "bucket_sort_perm",
 ]
 
 
@@ -59,6 +61,33 @@ def gather_rows(values: torch.Tensor, idx: torch.Tensor) -> torch.Tensor:
         return native.ext().gather_rows(values.contiguous(),
                                         idx.contiguous())
     return values[idx]
+
+
+_INT_KEY_DTYPES = (torch.int64, torch.int32, torch.int16, torch.int8,
+                   torch.bool)
+
+
+def bucket_sort_perm(key: torch.Tensor, bucket_ids: torch.Tensor,
+                     num_buckets: int):
+    """Fused (bucket, key) sort for one non-null integer key column on
+    the device: one stable sort of the composite
+    ``(bucket << S) | (normalized key - kmin)``.
+
+    Returns ``(perm, sorted_key, seg)``: the int32 permutation that sorts
+    the rows by (bucket, key) keeping source order among equals, the key
+    column already in that order, and the num_buckets + 1 segment offsets
+    (int64, CPU).  Returns None when the shape is not eligible: a CPU
+    tensor, a non-integer key, a key range too wide to sit beside the
+    bucket bits in 64 bits, fewer than 2 rows or 2^31 rows and more.
+    ``bucket_ids`` must lie in [0, num_buckets)."""
+    if (not isinstance(key, torch.Tensor) or not key.is_cuda
+            or not bucket_ids.is_cuda or key.dtype not in _INT_KEY_DTYPES
+            or not 1 < key.numel() < 1 << 31):
+        return None
+    res = native.ext().bucket_sort_perm(
+        key.contiguous(), bucket_ids.to(torch.int32).contiguous(),
+        num_buckets)
+    return None if res is None else tuple(res)
 
 
 def _is_cuda(*tensors: torch.Tensor) -> bool:
