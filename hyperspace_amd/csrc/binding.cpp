@@ -7,9 +7,11 @@
 #include <c10/hip/HIPStream.h>
 
 #include <algorithm>
+#include <string>
 #include <tuple>
 #include <vector>
 
+#include "bucket_writer.h"
 #include "kernels/kernels.h"
 
 namespace {
@@ -892,6 +894,118 @@ std::vector<torch::Tensor> segmented_reduce(torch::Tensor values,
 
 int64_t group_tile_size() { return hsk::group_tile_size(); }
 
+// All bucket files of one batch in one GIL-released call
+// (bucket_writer.h).  cols: 1-D contiguous int32/int64/float32/float64
+// tensors, all on one device or all on the host; stats: per (file, column)
+// PLAIN min/max bytes, file-major; ring: pinned uint8 staging of the
+// caller and stream0/stream1 the raw handles of two torch streams (device
+// batches; all three ignored for host batches).  Returns (sizes,
+// mtimes_ns, payload starts, payload ends), the last two file-major.
+std::tuple<std::vector<int64_t>, std::vector<int64_t>, std::vector<int64_t>,
+           std::vector<int64_t>>
+write_bucket_files(std::vector<torch::Tensor> cols,
+                   std::vector<std::string> names,
+                   std::vector<std::string> paths,
+                   std::vector<int64_t> row_lo, std::vector<int64_t> row_hi,
+                   std::vector<std::string> mins,
+                   std::vector<std::string> maxs, torch::Tensor ring,
+                   int64_t chunk_bytes, int64_t writer_threads,
+                   int64_t stream0, int64_t stream1, bool timing) {
+  TORCH_CHECK(!cols.empty() && cols.size() == names.size(),
+              "write_bucket_files: columns and names must be parallel");
+  TORCH_CHECK(paths.size() == row_lo.size() && paths.size() == row_hi.size(),
+              "write_bucket_files: paths and row ranges must be parallel");
+  TORCH_CHECK(mins.size() == paths.size() * cols.size() &&
+                  maxs.size() == mins.size(),
+              "write_bucket_files: one (min, max) per file and column");
+  TORCH_CHECK(chunk_bytes > 0 && writer_threads >= 1 && writer_threads <= 15,
+              "write_bucket_files: chunk_bytes > 0, 1 <= threads <= 15");
+  const bool on_device = cols[0].is_cuda();
+  const int64_t n = cols[0].numel();
+  std::vector<hsw::Column> wc;
+  for (size_t c = 0; c < cols.size(); c++) {
+    const torch::Tensor& t = cols[c];
+    TORCH_CHECK(t.dim() == 1 && t.is_contiguous() && t.numel() == n &&
+                    t.device() == cols[0].device(),
+                "write_bucket_files: columns must be 1-D, contiguous, of "
+                "one length and on one device");
+    int ptype;
+    switch (t.scalar_type()) {
+      case torch::kInt64: ptype = hsw::T_INT64; break;
+      case torch::kInt32: ptype = hsw::T_INT32; break;
+      case torch::kFloat64: ptype = hsw::T_DOUBLE; break;
+      case torch::kFloat32: ptype = hsw::T_FLOAT; break;
+      default:
+        TORCH_CHECK(false, "write_bucket_files: unsupported column dtype");
+    }
+    wc.push_back({t.data_ptr(), (int)t.element_size(), ptype, names[c]});
+  }
+  std::vector<hsw::FileJob> jobs;
+  for (size_t f = 0; f < paths.size(); f++) {
+    TORCH_CHECK(0 <= row_lo[f] && row_lo[f] < row_hi[f] && row_hi[f] <= n,
+                "write_bucket_files: row range of file ", f,
+                " is empty or outside the batch");
+    jobs.push_back({paths[f], row_lo[f], row_hi[f]});
+  }
+  std::vector<std::pair<std::string, std::string>> stats;
+  for (size_t i = 0; i < mins.size(); i++)
+    stats.emplace_back(std::move(mins[i]), std::move(maxs[i]));
+
+  hsw::Options opt;
+  opt.chunk_bytes = (size_t)chunk_bytes;
+  opt.writer_threads = (int)writer_threads;
+  opt.device_source = on_device;
+  opt.timing = timing;
+  std::vector<hsw::FileResult> res;
+  if (on_device) {
+    TORCH_CHECK(ring.device().is_cpu() && ring.is_pinned() &&
+                    ring.is_contiguous() &&
+                    ring.scalar_type() == torch::kUInt8 &&
+                    ring.numel() >= chunk_bytes,
+                "write_bucket_files: ring must be a pinned uint8 tensor of "
+                "at least one chunk");
+    // the caller has made the columns' device current
+    // two streams of torch's pool, handed in by the caller: the process
+    // opens few hardware queues, so none is created here
+    opt.streams[0] = reinterpret_cast<hipStream_t>(stream0);
+    opt.streams[1] = reinterpret_cast<hipStream_t>(stream1);
+    opt.ring = ring.data_ptr();
+    opt.ring_bytes = (size_t)ring.numel();
+    hipEvent_t start = nullptr;
+    TORCH_CHECK(hipEventCreateWithFlags(&start, hipEventDisableTiming) ==
+                    hipSuccess,
+                "write_bucket_files: hipEventCreate failed");
+    // the copies follow whatever the caller's stream has queued so far
+    hipError_t e = hipEventRecord(start, current_stream());
+    opt.start_event = start;
+    std::string err;
+    if (e != hipSuccess) {
+      err = std::string("hipEventRecord: ") + hipGetErrorString(e);
+    } else {
+      py::gil_scoped_release rel;
+      try {
+        res = hsw::write_bucket_files(wc, jobs, stats, opt);
+      } catch (const std::exception& ex) {
+        err = ex.what();
+      }
+    }
+    (void)hipEventDestroy(start);
+    TORCH_CHECK(err.empty(), err);
+  } else {
+    py::gil_scoped_release rel;
+    res = hsw::write_bucket_files(wc, jobs, stats, opt);
+  }
+  std::vector<int64_t> sizes, mtimes, starts, ends;
+  for (const hsw::FileResult& r : res) {
+    sizes.push_back(r.size);
+    mtimes.push_back(r.mtime_ns);
+    starts.insert(starts.end(), r.payload_start.begin(),
+                  r.payload_start.end());
+    ends.insert(ends.end(), r.payload_end.begin(), r.payload_end.end());
+  }
+  return {sizes, mtimes, starts, ends};
+}
+
 }  // namespace
 
 // out-of-namespace impl so the two-phase select is a single public symbol
@@ -962,6 +1076,9 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("keys"), py::arg("masks") = std::vector<torch::Tensor>{});
   m.def("segmented_reduce", &segmented_reduce,
         "fused per-group (sum, min, max, count); want bits 1/2/4");
+  m.def("write_bucket_files", &write_bucket_files,
+        "write every bucket file of a batch: chunked D2H through a pinned "
+        "ring into pwrite (host batches: pwrite from the columns)");
   m.def("group_tile_size", &group_tile_size,
         "rows per tile of the group-by kernels");
   m.def("snappy_decompress", &snappy_decompress,

@@ -15,6 +15,7 @@ all-to-all before the sort (C1, parallel/exchange.py).
 
 from __future__ import annotations
 
+import contextlib
 import os
 from typing import Any, Dict, List, Optional, Tuple
 
@@ -515,12 +516,153 @@ def sort_by_bucket_and_keys(batch: ColumnBatch, bucket_ids: torch.Tensor,
     return batch, seg
 
 
+_NATIVE_WRITE_DTYPES = (torch.int64, torch.int32, torch.float64,
+                        torch.float32)
+_WRITE_RING_SLOTS = 64
+
+
+def _native_write_eligible(batch: ColumnBatch) -> bool:
+    """The shape the native writer covers: the extension is loaded, every
+    column a non-string int64/int32/float64/float32 tensor, no masks.
+    HS_NATIVE_WRITE=0 (read per call) turns it off."""
+    if os.environ.get("HS_NATIVE_WRITE") == "0" or batch.masks:
+        return False
+    if not batch.columns or not ops.native.available():
+        return False
+    return all(not isinstance(c, StringColumn)
+               and c.dtype in _NATIVE_WRITE_DTYPES and c.dim() == 1
+               and c.device == batch.device
+               for c in batch.columns.values())
+
+
+def _device_stat_unusable(v) -> bool:
+    """The float-statistics rule.  The device reduce orders floats by
+    normalize_key (-NaN < -inf < -0.0 < +0.0 < +inf < +NaN), numpy's
+    min/max propagate NaN and pick between -0.0 and +0.0 by element order.
+    A NaN anywhere in a bucket, or a zero at either end of its range,
+    shows up as a NaN or a zero in the device min or max: such a (bucket,
+    column) pair takes its statistics from numpy on the host instead, so
+    the footer bytes stay those of write_parquet_native."""
+    return v != v or v == 0
+
+
+def _bucket_statistics(batch: ColumnBatch, jobs) -> Tuple[list, list]:
+    """PLAIN-encoded (min, max) of every (file, column), file-major.
+    Device batches: one segmented_reduce and one small D2H per column."""
+    from ...sources.native_parquet import _statistics
+    ncols = len(batch.columns)
+    mins = [b""] * (len(jobs) * ncols)
+    maxs = [b""] * (len(jobs) * ncols)
+    on_device = batch.device.type == "cuda"
+    offsets = torch.tensor([jobs[0][1]] + [j[2] for j in jobs],
+                           dtype=torch.int64)
+    for c, col in enumerate(batch.columns.values()):
+        mm = None
+        if on_device:
+            # the non-empty buckets tile [lo0, hi_last) with strictly
+            # ascending offsets, as the kernel requires
+            lo0, hi1 = jobs[0][1], jobs[-1][2]
+            red = ops.segmented_reduce(col[lo0:hi1], None, offsets - lo0,
+                                       want=("min", "max"))
+            mm = torch.stack([red["min"], red["max"]]).cpu().numpy()
+        for f, (_, lo, hi, _) in enumerate(jobs):
+            if mm is not None and not (
+                    col.dtype.is_floating_point
+                    and (_device_stat_unusable(mm[0, f])
+                         or _device_stat_unusable(mm[1, f]))):
+                mn, mx = mm[0, f].tobytes(), mm[1, f].tobytes()
+            else:
+                mn, mx = _statistics(col[lo:hi].cpu().numpy())
+            mins[f * ncols + c] = mn
+            maxs[f * ncols + c] = mx
+    return mins, maxs
+
+
+def _write_bucketed_native(batch: ColumnBatch, jobs,
+                           after_event: Optional["torch.cuda.Event"]
+                           ) -> List[str]:
+    """All bucket files of an eligible batch through the extension's
+    write_bucket_files: statistics from the device, then one GIL-released
+    call that streams chunks through a pinned ring into pwrite (host
+    batches: pwrite from the column memory).  HS_WRITE_CHUNK_MB and
+    HS_WRITE_THREADS override the chunk size and the writer thread
+    count."""
+    import time as _time
+    import numpy as np
+    from ...sources.native_parquet import (ColumnChunkLayout, Page,
+                                           _layout_cache_put)
+    from ...sources.staging import _pinned_get, _pinned_put
+    timing = os.environ.get("HS_TIMING")
+    t0 = _time.perf_counter()
+    on_device = batch.device.type == "cuda"
+    names = list(batch.columns.keys())
+    cols = [c.contiguous() for c in batch.columns.values()]
+    chunk = max(1, int(float(os.environ.get("HS_WRITE_CHUNK_MB", "8"))
+                       * (1 << 20)))
+    # copier + writers stay within the 16 CPUs a process is given
+    threads = min(15, max(1, int(os.environ.get("HS_WRITE_THREADS", "15"))))
+    paths = [j[3] for j in jobs]
+    row_lo = [j[1] for j in jobs]
+    row_hi = [j[2] for j in jobs]
+    ring = None
+    streams = (0, 0)
+    if on_device:
+        if after_event is not None:
+            torch.cuda.current_stream(batch.device).wait_event(after_event)
+        # no chunk is larger than the largest column payload, and the
+        # ring never holds more slots than there are chunks
+        esz = max(c.element_size() for c in cols)
+        largest = max(hi - lo for lo, hi in zip(row_lo, row_hi)) * esz
+        chunk = min(chunk, -(-largest // 4096) * 4096)
+        n_chunks = sum(-(-(hi - lo) * c.element_size() // chunk)
+                       for lo, hi in zip(row_lo, row_hi) for c in cols)
+        ring = _pinned_get(chunk * max(2, min(_WRITE_RING_SLOTS, n_chunks)))
+    try:
+        with torch.cuda.device(batch.device) if on_device \
+                else contextlib.nullcontext():
+            mins, maxs = _bucket_statistics(batch, jobs)
+            t1 = _time.perf_counter()
+            if on_device:
+                pool = [torch.cuda.Stream(device=batch.device)
+                        for _ in range(2)]
+                streams = tuple(s.cuda_stream for s in pool)
+            sizes, mtimes, starts, ends = ops.native.ext().write_bucket_files(
+                cols, names, paths, row_lo, row_hi, mins, maxs,
+                ring if ring is not None
+                else torch.empty(0, dtype=torch.uint8),
+                chunk, threads, streams[0], streams[1], bool(timing))
+    finally:
+        if ring is not None:
+            _pinned_put(ring)
+    ncols = len(cols)
+    np_dtypes = [np.dtype(str(c.dtype).replace("torch.", "")) for c in cols]
+    for f, path in enumerate(paths):
+        rows = row_hi[f] - row_lo[f]
+        _layout_cache_put(path, rows, [
+            ColumnChunkLayout(
+                names[c], np_dtypes[c],
+                [Page("plain", starts[f * ncols + c], ends[f * ncols + c],
+                      rows)], rows, "plain", None, [None])
+            for c in range(ncols)], (sizes[f], mtimes[f]))
+    if timing:
+        import sys as _sys
+        t2 = _time.perf_counter()
+        print(f"[hs-timing] native write: stats {t1-t0:.3f}s "
+              f"files {t2-t1:.3f}s ({len(paths)} files, chunk {chunk} B, "
+              f"{threads} writers)", file=_sys.stderr)
+    return paths
+
+
 def write_bucketed(batch: ColumnBatch, seg: torch.Tensor, out_dir: str,
                    num_buckets: int, task_id: int = 0,
                    after_event: Optional["torch.cuda.Event"] = None
                    ) -> List[str]:
     """Write per-bucket parquet files honoring the bucket-id filename
     contract.  Empty buckets produce no file (as in Spark).
+
+    The common shape (see _native_write_eligible, and more than two
+    files) goes through the extension's native writer; the files are the
+    same bytes either way.  Everything else runs the Python writer below.
 
     Files are written by a thread pool: the native encoder's byte
     assembly (numpy tobytes) and os.write both release the GIL, so the
@@ -532,33 +674,6 @@ def write_bucketed(batch: ColumnBatch, seg: torch.Tensor, out_dir: str,
     from ...execution.columnar import StringColumn
     from ...sources.parquet_io import _pinned_get, _pinned_put
     on_device = batch.device.type == "cuda"
-    if on_device and os.environ.get("HS_WRITE_V2"):
-        # A/B variant: ONE bulk pinned D2H per column, then the bucket
-        # files slice host memory (no per-bucket device copies)
-        if after_event is not None:
-            torch.cuda.current_stream().wait_event(after_event)
-        host_cols = {}
-        host_masks = {}
-        held_bufs = []
-        for name, col in batch.columns.items():
-            if isinstance(col, StringColumn):
-                host_cols[name] = col.to("cpu")
-                continue
-            nb = col.numel() * col.element_size()
-            bufp = _pinned_get(nb)
-            host = bufp[:nb].view(col.dtype)
-            host.copy_(col, non_blocking=True)
-            host_cols[name] = host
-            held_bufs.append(bufp)
-        for name, m in batch.masks.items():
-            host_masks[name] = m.to("cpu")
-        torch.cuda.current_stream().synchronize()
-        host_batch = ColumnBatch(host_cols, host_masks)
-        out = write_bucketed(host_batch, seg, out_dir, num_buckets,
-                             task_id)
-        for bufp in held_bufs:
-            _pinned_put(bufp)
-        return out
     jobs = []
     for b in range(num_buckets):
         lo, hi = int(seg[b]), int(seg[b + 1])
@@ -566,6 +681,9 @@ def write_bucketed(batch: ColumnBatch, seg: torch.Tensor, out_dir: str,
             continue
         jobs.append((b, lo, hi,
                      os.path.join(out_dir, bucket_file_name(task_id, b))))
+
+    if len(jobs) > 2 and _native_write_eligible(batch):
+        return _write_bucketed_native(batch, jobs, after_event)
 
     # per-worker HIP streams + pooled pinned staging: pageable D2H runs
     # at ~13 GB/s, pinned at ~53 GB/s, and per-bucket copies on separate

@@ -45,11 +45,11 @@ class ScoreBasedIndexPlanOptimizer:
         return best
 
     def _rec_apply(self, plan: LogicalPlan, candidates,
-                   memo: Dict[int, Tuple[LogicalPlan, float]]
+                   memo: Dict[int, tuple]
                    ) -> Tuple[LogicalPlan, float]:
         key = id(plan)
         if key in memo:
-            return memo[key]
+            return memo[key][:2]
         best_plan, best_score = plan, -1.0
         for rule in self.rules:
             transformed, score = rule.apply(plan, candidates)
@@ -66,5 +66,8 @@ class ScoreBasedIndexPlanOptimizer:
                     if child_results else transformed)
                 if total > best_score:
                     best_plan, best_score = candidate_plan, total
-        memo[key] = (best_plan, max(best_score, 0.0))
-        return memo[key]
+        # the entry holds ``plan`` itself: a rule's transformed children
+        # are temporaries, and once one is freed a later rule's child can
+        # get its id and would read this entry as its own
+        memo[key] = (best_plan, max(best_score, 0.0), plan)
+        return memo[key][:2]

@@ -326,13 +326,18 @@ def layout_cache_get(path: str):
     return ent[1], ent[2]
 
 
-def _layout_cache_put(path: str, num_rows: int, layouts: list) -> None:
+def _layout_cache_put(path: str, num_rows: int, layouts: list,
+                      stat: Optional[Tuple[int, int]] = None) -> None:
+    """``stat``: the file's (size, mtime_ns) when the writer already has
+    them (the native bucket writer's fstat), else it is stat'ed here."""
     if len(_LAYOUT_CACHE) >= _LAYOUT_CACHE_MAX:
         # FIFO evict ~1/8th
         for k in list(_LAYOUT_CACHE)[:_LAYOUT_CACHE_MAX // 8]:
             _LAYOUT_CACHE.pop(k, None)
-    st = os.stat(path)
-    _LAYOUT_CACHE[path] = ((st.st_size, st.st_mtime_ns), num_rows, layouts)
+    if stat is None:
+        st = os.stat(path)
+        stat = (st.st_size, st.st_mtime_ns)
+    _LAYOUT_CACHE[path] = (tuple(stat), num_rows, layouts)
 
 
 def write_parquet_native(columns: "Dict[str, np.ndarray]", path: str,

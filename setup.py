@@ -26,6 +26,7 @@ setup(
             name="hyperspace_amd._hip",
             sources=[
                 "hyperspace_amd/csrc/binding.cpp",
+                "hyperspace_amd/csrc/bucket_writer.cpp",
                 "hyperspace_amd/csrc/kernels/kernels.hip",
                 "hyperspace_amd/csrc/kernels/aggregate.hip",
             ],
