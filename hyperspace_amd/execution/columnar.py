@@ -282,7 +282,17 @@ class ColumnBatch:
                             pairs.append((leaf, child))
             else:
                 pairs.append((name, col))
+        from ..sources.logical_types import arrow_engine_type
         for name, col in pairs:
+            if not pa.types.is_decimal(col.type):
+                # the engine representation of the column's logical type
+                # (dates -> int32 days, small unsigned -> int32, uint32 ->
+                # int64; time / binary / uint64 are refused)
+                cast_to = arrow_engine_type(name, col.type)
+                if cast_to is not None:
+                    if pa.types.is_date64(col.type):
+                        col = col.cast(pa.date32())
+                    col = col.cast(cast_to)
             if col.null_count:
                 masks[name] = torch.from_numpy(
                     np.ascontiguousarray(col.is_valid().to_numpy(
@@ -290,6 +300,8 @@ class ColumnBatch:
                 if pa.types.is_string(col.type) or \
                         pa.types.is_large_string(col.type):
                     col = col.fill_null("")
+                elif pa.types.is_boolean(col.type):
+                    col = col.fill_null(False)
                 else:
                     col = col.fill_null(0)
             if pa.types.is_string(col.type) or pa.types.is_large_string(

@@ -767,6 +767,7 @@ class Executor:
 
 _SPARK_DTYPES = {"long": torch.int64, "integer": torch.int32,
                  "short": torch.int16, "byte": torch.int8,
+                 "date": torch.int32,  # days; hashes as int, like Spark
                  "double": torch.float64, "float": torch.float32}
 
 

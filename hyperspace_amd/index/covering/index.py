@@ -317,6 +317,7 @@ class CoveringIndex(Index):
         import torch as _torch
         dts = {"long": _torch.int64, "integer": _torch.int32,
                "short": _torch.int16, "byte": _torch.int8,
+               "date": _torch.int32,
                "double": _torch.float64, "float": _torch.float32,
                "boolean": _torch.bool}
         cols: Dict[str, Any] = {}

@@ -38,6 +38,10 @@ _PYARROW_TO_SPARK = {
     "float": "float", "double": "double", "string": "string",
     "large_string": "string", "bool": "boolean", "date32[day]": "date",
     "timestamp[us]": "timestamp", "timestamp[ns]": "timestamp",
+    "timestamp[ms]": "timestamp", "date64[ms]": "date",
+    # unsigned integers are named by the signed type that holds them in
+    # the engine (sources/logical_types.py)
+    "uint8": "integer", "uint16": "integer", "uint32": "long",
     "binary": "binary",
 }
 

@@ -16,6 +16,7 @@ from typing import Dict, List, NamedTuple, Optional, Tuple
 import numpy as np
 import torch
 
+from .logical_types import convert_torch
 from .native_parquet import _decode_defs, decode_splain_pages
 from .staging import _DEV_RATIO, _codec_pool, _pinned_get, _tl_decompress
 
@@ -39,6 +40,14 @@ class DecodeState:
         field(default_factory=list)
     # pinned codec staging buffers, alive until the streams drain
     keepalive: List[torch.Tensor] = field(default_factory=list)
+
+
+def convert_logical(col: torch.Tensor, conv) -> torch.Tensor:
+    """The convert step of the device read: a decoded PHYSICAL column ->
+    its engine representation (logical_types.Conv), one elementwise torch
+    op on the current stream.  Runs once per annotated column after the
+    decode streams have joined; un-annotated columns never reach it."""
+    return convert_torch(col, conv)
 
 
 def split_row_groups(chunks):

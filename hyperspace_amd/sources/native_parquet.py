@@ -27,6 +27,8 @@ from typing import Any, Dict, List, NamedTuple, Optional, Tuple
 
 import numpy as np
 
+from .logical_types import convert_np, parquet_convs
+
 MAGIC = b"PAR1"
 
 # parquet physical types
@@ -571,18 +573,23 @@ class ColumnChunkLayout:
     OPTIONAL columns with nulls in that page, else None.  A page's stored
     values are compacted (non-null only); num values counts rows.
 
+    ``np_dtype`` is the PHYSICAL dtype the pages decode as; ``conv`` is
+    the logical_types.Conv that turns the assembled physical column into
+    its engine representation, None when they are the same.
+
     ``is_string``: BYTE_ARRAY dictionary chunk — decoded values are int32
     codes into ``str_values`` (parsed lazily from the dictionary page
     when not supplied by the writer's layout cache).
     """
     __slots__ = ("name", "np_dtype", "pages", "num_values", "encoding",
                  "dict_page", "page_masks", "is_string", "str_values",
-                 "codec", "max_def")
+                 "codec", "max_def", "conv")
 
     def __init__(self, name, np_dtype, pages, num_values,
                  encoding="plain", dict_page=None, page_masks=None,
                  is_string=False, str_values=None,
-                 codec="UNCOMPRESSED", max_def=1):
+                 codec="UNCOMPRESSED", max_def=1, conv=None):
+        self.conv = conv
         self.name = name
         self.np_dtype = np_dtype
         self.pages = pages
@@ -709,18 +716,20 @@ def read_native_layout(path: str,
             data = f.read()
     out: List[ColumnChunkLayout] = []
     want = {c.lower() for c in columns} if columns is not None else None
+    # refused logical types raise here, before any page is walked
+    convs = parquet_convs(pf_schema, want)
     # row-group-major walk: large files carry many row groups; each
     # column chunk (and its dictionary) is per-row-group
     for rg_i in range(md.num_row_groups):
         rg = md.row_group(rg_i)
-        lay = _walk_row_group(rg, pf_schema, data, want)
+        lay = _walk_row_group(rg, pf_schema, data, want, convs)
         if lay is None:
             return None
         out.extend(lay)
     return data, out
 
 
-def _walk_row_group(rg, pf_schema, data, want
+def _walk_row_group(rg, pf_schema, data, want, convs
                     ) -> Optional[List[ColumnChunkLayout]]:
     out: List[ColumnChunkLayout] = []
     for i in range(rg.num_columns):
@@ -730,6 +739,7 @@ def _walk_row_group(rg, pf_schema, data, want
         lay = _walk_chunk(col, pf_schema.column(i), data)
         if lay is None:
             return None
+        lay.conv = convs.get(i)
         out.append(lay)
     return out
 
@@ -1095,6 +1105,7 @@ def read_native_host(path: str, columns: Optional[List[str]] = None
     macc: Dict[str, list] = {}
     any_null: Dict[str, bool] = {}
     str_dicts: Dict[str, list] = {}
+    convs = {c.name: c.conv for c in chunks if c.conv is not None}
     for c in chunks:  # row-group-major order
         if not c.pages:  # zero-row chunk still contributes its column
             acc.setdefault(c.name, []).append(
@@ -1175,6 +1186,10 @@ def read_native_host(path: str, columns: Optional[List[str]] = None
                 # a value to dereference
                 merged_vals = [""]
             cols[name] = StrCol(codes, list(merged_vals))
+        elif name in convs:
+            cols[name] = convert_np(
+                np.concatenate(parts) if len(parts) > 1 else parts[0],
+                convs[name])
         else:
             cols[name] = (np.concatenate(parts) if len(parts) > 1
                           else (parts[0] if parts[0].flags.writeable

@@ -26,7 +26,11 @@ from typing import Dict, List, NamedTuple, Optional, Tuple
 import numpy as np
 import torch
 
-from .device_decode import DecodeState, decode_chunks, split_row_groups
+from ..exceptions import HyperspaceException
+from .device_decode import (DecodeState, convert_logical, decode_chunks,
+                            split_row_groups)
+from .logical_types import (Conv, check_parquet_file, parquet_convs,
+                            to_storage_np)
 from .native_parquet import (StrCol, layout_cache_get, merge_string_dicts,
                              read_native_layout, string_remap_tables)
 from .staging import _DEV_RATIO, _pinned_get, _pinned_put  # noqa: F401
@@ -102,6 +106,7 @@ def _pyarrow_file_dict(p, columns):
     native and fallback files."""
     import pyarrow.parquet as pq
     from ..execution.columnar import ColumnBatch, StringColumn
+    check_parquet_file(p, columns)  # same refusals as the native walk
     t = pq.read_table(p, columns=_resolve_read_columns(p, columns))
     b = ColumnBatch.from_arrow(t)
     if columns is not None:
@@ -138,6 +143,8 @@ def read_files_batch(paths: List[str], columns: Optional[List[str]] = None):
             per_file.append(cols)
             per_file_masks.append(fmasks)
             row_counts.append(n)
+    except HyperspaceException:  # a refused logical type
+        raise
     except Exception:  # exotic schema mix: whole-batch pyarrow path
         native_ok = False
         row_counts = []
@@ -183,6 +190,7 @@ def read_files_batch(paths: List[str], columns: Optional[List[str]] = None):
     tables = []
     row_counts = []
     for p in paths:
+        check_parquet_file(p, columns)
         t = pq.read_table(p, columns=_resolve_read_columns(p, columns))
         tables.append(t)
         row_counts.append(t.num_rows)
@@ -208,7 +216,8 @@ class _ReadPlan(NamedTuple):
     """What the footers (or the writer's layout cache) say about a batch
     of files, enough to size the output before any file is read."""
     names: List[str]               # output columns, in output order
-    dtypes: Dict[str, np.dtype]
+    dtypes: Dict[str, np.dtype]    # PHYSICAL dtype the decoders write
+    convs: Dict[str, Conv]         # columns converted after the decode
     row_counts: List[int]
     nullable_cols: set
     string_cols: set
@@ -222,6 +231,7 @@ def _plan_from_cache(cached, want) -> _ReadPlan:
     return _ReadPlan(
         [c.name for c in lay0 if want is None or c.name.lower() in want],
         {c.name: c.np_dtype for c in lay0},
+        {c.name: c.conv for c in lay0 if c.conv is not None},
         [ent[0] for ent in cached],
         {c.name for ent in cached for c in ent[1] if c.has_nulls},
         {c.name for ent in cached for c in ent[1] if c.is_string},
@@ -240,6 +250,8 @@ def _plan_from_footers(paths, want) -> Optional[_ReadPlan]:
             return None
         metas.append(pf.metadata)
         schemas.append(pf.schema)
+    # refused logical types raise here: nothing is allocated or launched
+    file_convs = [parquet_convs(sch, want) for sch in schemas]
     # column nullability from chunk statistics (sizes the preallocated
     # masks); an OPTIONAL chunk without statistics could hide nulls ->
     # the host path decides instead
@@ -258,6 +270,7 @@ def _plan_from_footers(paths, want) -> Optional[_ReadPlan]:
     rg0 = metas[0].row_group(0)
     names = []
     dtypes = {}
+    convs = {}
     string_cols = set()
     for ci in range(rg0.num_columns):
         col = rg0.column(ci)
@@ -287,7 +300,9 @@ def _plan_from_footers(paths, want) -> Optional[_ReadPlan]:
                 return None
         names.append(name)
         dtypes[name] = npd
-    return _ReadPlan(names, dtypes, [md.num_rows for md in metas],
+        if ci in file_convs[0]:
+            convs[name] = file_convs[0][ci]
+    return _ReadPlan(names, dtypes, convs, [md.num_rows for md in metas],
                      nullable_cols, string_cols, None, metas, schemas)
 
 
@@ -372,7 +387,10 @@ class _DeviceRead:
                                           arr.values))
                     arr = arr.codes
                 else:
-                    arr = arr.astype(plan.dtypes[name], copy=False)
+                    # engine representation -> the physical dtype the
+                    # batch stores until its convert step (a uint32
+                    # column travels as its int32 bit pattern)
+                    arr = to_storage_np(arr, plan.dtypes[name])
                 st.out[name][base:base + n] = torch.from_numpy(
                     np.ascontiguousarray(arr)).to(st.device,
                                                   non_blocking=True)
@@ -507,4 +525,6 @@ def read_files_batch_device(paths: List[str], device,
         return fallback()
     if plan.string_cols:
         _merge_string_columns(st, plan.string_cols)
+    for name, conv in plan.convs.items():
+        st.out[name] = convert_logical(st.out[name], conv)
     return ColumnBatch(st.out, st.out_masks), plan.row_counts

@@ -56,11 +56,26 @@ def _infer_partition_type(values: List[str]) -> str:
 
 
 def _cast_partition_value(v: str, spark_type: str) -> Any:
-    if spark_type == "long":
+    if spark_type in ("long", "integer", "short", "byte"):
         return int(v)
-    if spark_type == "double":
+    if spark_type in ("double", "float"):
         return float(v)
+    if spark_type == "date":
+        # days since the epoch, the engine's date representation; the
+        # path segment / partitionValues entry is an ISO date
+        import datetime
+        if isinstance(v, str) and "-" in v.lstrip("-"):
+            return (datetime.date.fromisoformat(v)
+                    - datetime.date(1970, 1, 1)).days
+        return int(v)
     return v
+
+
+# engine tensor of a numeric partition column, by the table of
+# sources/logical_types.py: a partition column must hash to the same
+# bucket as the same values read from a file column
+_PARTITION_DTYPES = {"long": "int64", "integer": "int32", "date": "int32",
+                     "short": "int16", "byte": "int8"}
 
 
 def _is_data_file(name: str) -> bool:
@@ -235,8 +250,7 @@ def partitioned_read_files(relation, paths: List[str], columns, device,
                 if row_counts else torch.empty(0, dtype=torch.int32)
             cols[f.name] = StringColumn(codes.to(dev), uniq)
         else:
-            dt = torch.int64 if f.type in ("long", "integer", "date") \
-                else torch.float64
+            dt = getattr(torch, _PARTITION_DTYPES.get(f.type, "float64"))
             cols[f.name] = torch.cat([
                 torch.full((rc,), v, dtype=dt)
                 for v, rc in zip(vals, row_counts)]).to(dev) \

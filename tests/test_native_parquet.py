@@ -14,6 +14,7 @@ from hyperspace_amd.sources.native_parquet import (
 from hyperspace_amd.sources.parquet_io import (read_files_batch,
                                                write_batch_parquet)
 from hyperspace_amd.execution.columnar import ColumnBatch
+from hyperspace_amd.exceptions import HyperspaceException
 
 
 @pytest.fixture
@@ -104,8 +105,17 @@ def test_fallback_on_compressed(tmp_path, cols):
     import decimal
     pq.write_table(pa.table({"d": pa.array(
         [decimal.Decimal("1.23")] * 100,
-        type=pa.decimal128(20, 2))}), p5)
+        type=pa.decimal128(12, 2))}), p5)
+    assert pq.ParquetFile(p5).schema.column(0).physical_type == \
+        "FIXED_LEN_BYTE_ARRAY"
     assert read_native_layout(p5) is None
+    # ... and past the engine's p <= 18 limit the column is refused by
+    # name instead of declined
+    pq.write_table(pa.table({"d": pa.array(
+        [decimal.Decimal("1.23")] * 100,
+        type=pa.decimal128(20, 2))}), p5)
+    with pytest.raises(HyperspaceException, match="'d'"):
+        read_native_layout(p5)
 
 
 def test_write_batch_parquet_uses_native(tmp_path, cols):
