@@ -34,6 +34,8 @@ class IndexConstants:
         "spark.hyperspace.index.filterRule.useBucketSpec")
     INDEX_AGGREGATE_RULE_ENABLED = (
         "spark.hyperspace.index.aggregateRule.enabled")
+    INDEX_TOPK_RULE_ENABLED = (
+        "spark.hyperspace.index.topKRule.enabled")
     OPTIMIZE_FILE_SIZE_THRESHOLD = (
         "spark.hyperspace.index.optimize.fileSizeThreshold")
     OPTIMIZE_FILE_SIZE_THRESHOLD_DEFAULT = 256 * 1024 * 1024
@@ -84,6 +86,7 @@ _DEFAULTS: Dict[str, Any] = {
     IndexConstants.INDEX_LINEAGE_ENABLED: False,
     IndexConstants.INDEX_FILTER_RULE_USE_BUCKET_SPEC: False,
     IndexConstants.INDEX_AGGREGATE_RULE_ENABLED: True,
+    IndexConstants.INDEX_TOPK_RULE_ENABLED: True,
     IndexConstants.OPTIMIZE_FILE_SIZE_THRESHOLD:
         IndexConstants.OPTIMIZE_FILE_SIZE_THRESHOLD_DEFAULT,
     IndexConstants.APPLY_HYPERSPACE_ENABLED: True,
@@ -165,6 +168,10 @@ class Conf:
     @property
     def aggregate_rule_enabled(self) -> bool:
         return bool(self.get(IndexConstants.INDEX_AGGREGATE_RULE_ENABLED))
+
+    @property
+    def topk_rule_enabled(self) -> bool:
+        return bool(self.get(IndexConstants.INDEX_TOPK_RULE_ENABLED))
 
     @property
     def optimize_file_size_threshold(self) -> int:

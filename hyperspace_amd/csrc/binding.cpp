@@ -113,7 +113,8 @@ torch::Tensor murmur3_bucket(std::vector<torch::Tensor> keys,
   return out;
 }
 
-torch::Tensor normalize_key(torch::Tensor vals, bool canonical = false) {
+torch::Tensor normalize_key(torch::Tensor vals, bool canonical = false,
+                            bool descending = false) {
   check_cuda(vals, "vals");
   auto n = vals.numel();
   auto out = torch::empty(
@@ -121,7 +122,7 @@ torch::Tensor normalize_key(torch::Tensor vals, bool canonical = false) {
   hsk::normalize_key(vals.data_ptr(),
                      normalize_dtype_code(vals.scalar_type()),
                      (uint64_t*)out.data_ptr<int64_t>(), n,
-                     current_stream(), canonical);
+                     current_stream(), canonical, descending);
   return out;
 }
 
@@ -894,6 +895,44 @@ std::vector<torch::Tensor> segmented_reduce(torch::Tensor values,
 
 int64_t group_tile_size() { return hsk::group_tile_size(); }
 
+// Rows of the k smallest u64 keys (int64-encoded), ascending row index;
+// valid: empty = all rows.  The one host read is the output length.
+torch::Tensor topk_rows(torch::Tensor keys, int64_t k, torch::Tensor valid,
+                        bool keep_ties) {
+  check_cuda(keys, "keys");
+  TORCH_CHECK(keys.scalar_type() == torch::kInt64,
+              "keys must be normalized int64");
+  int64_t n = keys.numel();
+  auto opts = torch::dtype(torch::kInt64).device(keys.device());
+  if (n == 0 || k <= 0) return torch::empty({0}, opts);
+  if (k > n) k = n;
+  keys = aligned16(keys);
+  const uint8_t* vptr = nullptr;
+  if (valid.numel() > 0) {
+    check_cuda(valid, "valid");
+    TORCH_CHECK(valid.numel() == n, "valid length mismatch");
+    TORCH_CHECK(valid.scalar_type() == torch::kBool ||
+                    valid.scalar_type() == torch::kUInt8,
+                "valid must be bool/uint8");
+    valid = aligned16(valid);
+    vptr = (const uint8_t*)valid.data_ptr();
+  }
+  auto stream = current_stream();
+  auto scratch = torch::zeros({hsk::topk_scratch_size(n)}, opts);
+  const uint64_t* kp = (const uint64_t*)keys.data_ptr<int64_t>();
+  int64_t* d_total = hsk::topk_select(kp, vptr, n, k, keep_ties,
+                                      scratch.data_ptr<int64_t>(), stream);
+  int64_t idx = d_total - scratch.data_ptr<int64_t>();
+  int64_t n_out = scratch.narrow(0, idx, 1).cpu().item<int64_t>();
+  TORCH_CHECK(n_out >= 0 && n_out <= n, "topk_rows: bad output length");
+  auto out = torch::empty({n_out}, opts);
+  hsk::topk_emit(kp, vptr, n, scratch.data_ptr<int64_t>(),
+                 out.data_ptr<int64_t>(), n_out, stream);
+  return out;
+}
+
+int64_t topk_tile_size() { return hsk::topk_tile_size(); }
+
 // All bucket files of one batch in one GIL-released call
 // (bucket_writer.h).  cols: 1-D contiguous int32/int64/float32/float64
 // tensors, all on one device or all on the host; stats: per (file, column)
@@ -1044,7 +1083,8 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("keys"), py::arg("num_buckets"),
         py::arg("masks") = std::vector<torch::Tensor>{});
   m.def("normalize_key", &normalize_key, "order-preserving u64 key",
-        py::arg("vals"), py::arg("canonical") = false);
+        py::arg("vals"), py::arg("canonical") = false,
+        py::arg("descending") = false);
   m.def("radix_sort_pairs", &radix_sort_pairs, "stable LSD radix sort");
   m.def("radix_sort_plan", &radix_sort_plan,
         "pass plan of the radix sort for a varying-bit mask: "
@@ -1081,6 +1121,12 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         "ring into pwrite (host batches: pwrite from the columns)");
   m.def("group_tile_size", &group_tile_size,
         "rows per tile of the group-by kernels");
+  m.def("topk_rows", &topk_rows,
+        "rows of the k smallest keys by radix select, ascending row index",
+        py::arg("keys"), py::arg("k"), py::arg("valid"),
+        py::arg("keep_ties") = false);
+  m.def("topk_tile_size", &topk_tile_size,
+        "rows per tile of the top-k kernels");
   m.def("snappy_decompress", &snappy_decompress,
         "device snappy raw-block page decompression; returns status");
   m.def("decode_def_levels", &decode_def_levels,

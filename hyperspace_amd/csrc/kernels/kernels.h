@@ -1,5 +1,5 @@
 // Host-side API of the CDNA4 kernel suite (pure HIP, gfx950).
-// Implemented in kernels.hip and aggregate.hip; called from the torch
+// Implemented in kernels.hip, aggregate.hip and topk.hip; called from the torch
 // binding (binding.cpp).
 #pragma once
 
@@ -28,8 +28,15 @@ void murmur3_last_column(const void* vals, int kind, const uint8_t* valid,
 // order-preserving u64 normalization (dtype codes: 0=i64,1=i32,2=f64,3=f32,
 // 4=i16, 5=i8, 6=bool/u8).  canonical: float zeros and NaNs collapse first
 // (SQL equality: the key of -0.0 is that of +0.0, all NaNs share the top key)
+// descending: the bitwise complement of that key, so ascending u64 order of
+// the result is descending order of the values (ORDER BY ... DESC).
 void normalize_key(const void* vals, int dtype, uint64_t* out, int64_t n,
-                   hipStream_t stream, bool canonical = false);
+                   hipStream_t stream, bool canonical = false,
+                   bool descending = false);
+// d_mask[0] |= OR over i of (keys[i] ^ keys[0]): a superset of the key bits
+// that vary.  d_mask must hold 0 (or bits to keep) on entry.
+void key_varying_bits(const uint64_t* keys, int64_t n, uint64_t* d_mask,
+                      hipStream_t stream);
 
 // K3: stable LSD radix sort of (u64 key, i64 payload), ascending u64 order.
 // keys/payload are sorted in place; tmp buffers same size provided by caller.
@@ -179,6 +186,28 @@ void segmented_reduce(const void* vals, int dtype, const uint8_t* valid,
                       void* sums, void* mins, void* maxs, int64_t* counts,
                       int64_t* tile_groups, int64_t* partials,
                       hipStream_t stream);
+
+// K14 (topk.hip): rows of the k smallest keys, without sorting.  Over the
+// rows with valid[i] != 0 (all rows when valid is null) let T be the k-th
+// smallest key in u64 order.  The result is, in ascending row index, every
+// valid row with key < T and then of the rows with key == T either all of
+// them (keep_ties) or the first k - #less in row order.  k > n_valid gives
+// every valid row.  The stored key of an invalid row is ignored.
+// Two-phase like select_range: topk_select finds T (MSD radix select,
+// 8-bit digits, no host read between passes) and counts; it returns the
+// device address of the output length.  After reading it the caller sizes
+// out and runs topk_emit with the same keys, valid and scratch.
+// n >= 1, 1 <= k <= n.  scratch: topk_scratch_size(n) int64 entries, ZEROED
+// by the caller.  keys and valid must be 16-byte aligned.
+int64_t topk_tile_size();
+int64_t topk_num_blocks(int64_t n);
+int64_t topk_scratch_size(int64_t n);
+int64_t* topk_select(const uint64_t* keys, const uint8_t* valid, int64_t n,
+                     int64_t k, bool keep_ties, int64_t* scratch,
+                     hipStream_t stream);
+void topk_emit(const uint64_t* keys, const uint8_t* valid, int64_t n,
+               const int64_t* scratch, int64_t* out, int64_t n_out,
+               hipStream_t stream);
 
 // K8: bloom filter build/probe (k hashes, m_bits bits over u64 words)
 void bloom_build(const int64_t* vals, int64_t n, uint64_t* words,

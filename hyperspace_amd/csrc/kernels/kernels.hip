@@ -193,25 +193,30 @@ void murmur3_last_column(const void* vals, int kind, const uint8_t* valid,
 // Order-preserving u64 key normalization
 // ---------------------------------------------------------------------------
 
-__global__ void k_norm_i64(const int64_t* in, uint64_t* out, int64_t n) {
+// flip: 0, or all ones for a descending order key (the complement of the
+// ascending key), in every kernel below.
+__global__ void k_norm_i64(const int64_t* in, uint64_t* out, int64_t n,
+                           uint64_t flip) {
   int64_t stride = (int64_t)gridDim.x * blockDim.x;
   for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n;
        i += stride)
-    out[i] = (uint64_t)in[i] ^ 0x8000000000000000ull;
+    out[i] = (uint64_t)in[i] ^ 0x8000000000000000ull ^ flip;
 }
 
 template <typename T>
-__global__ void k_norm_small_int(const T* in, uint64_t* out, int64_t n) {
+__global__ void k_norm_small_int(const T* in, uint64_t* out, int64_t n,
+                                 uint64_t flip) {
   int64_t stride = (int64_t)gridDim.x * blockDim.x;
   for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n;
        i += stride)
-    out[i] = (uint64_t)(int64_t)in[i] ^ 0x8000000000000000ull;
+    out[i] = (uint64_t)(int64_t)in[i] ^ 0x8000000000000000ull ^ flip;
 }
 
 // CANON: the SQL-equality key (ops.sql_key) — zeros and NaNs collapse as
 // in canon_f64_bits before the order-preserving flip, in the same pass.
 template <bool CANON>
-__global__ void k_norm_f64(const double* in, uint64_t* out, int64_t n) {
+__global__ void k_norm_f64(const double* in, uint64_t* out, int64_t n,
+                           uint64_t flip) {
   int64_t stride = (int64_t)gridDim.x * blockDim.x;
   for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n;
        i += stride) {
@@ -219,12 +224,13 @@ __global__ void k_norm_f64(const double* in, uint64_t* out, int64_t n) {
     if (CANON) bits = (int64_t)canon_f64_bits((uint64_t)bits);
     uint64_t mask =
         bits < 0 ? 0xFFFFFFFFFFFFFFFFull : 0x8000000000000000ull;
-    out[i] = (uint64_t)bits ^ mask;
+    out[i] = (uint64_t)bits ^ mask ^ flip;
   }
 }
 
 template <bool CANON>
-__global__ void k_norm_f32(const float* in, uint64_t* out, int64_t n) {
+__global__ void k_norm_f32(const float* in, uint64_t* out, int64_t n,
+                           uint64_t flip) {
   int64_t stride = (int64_t)gridDim.x * blockDim.x;
   for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n;
        i += stride) {
@@ -233,49 +239,50 @@ __global__ void k_norm_f32(const float* in, uint64_t* out, int64_t n) {
     if (CANON) bits = (int64_t)canon_f64_bits((uint64_t)bits);
     uint64_t mask =
         bits < 0 ? 0xFFFFFFFFFFFFFFFFull : 0x8000000000000000ull;
-    out[i] = (uint64_t)bits ^ mask;
+    out[i] = (uint64_t)bits ^ mask ^ flip;
   }
 }
 
 void normalize_key(const void* vals, int dtype, uint64_t* out, int64_t n,
-                   hipStream_t stream, bool canonical) {
+                   hipStream_t stream, bool canonical, bool descending) {
   int g = grid_for(n);
+  uint64_t flip = descending ? ~0ull : 0ull;
   switch (dtype) {
     case 0:
       hipLaunchKernelGGL(k_norm_i64, dim3(g), dim3(THREADS), 0, stream,
-                         (const int64_t*)vals, out, n);
+                         (const int64_t*)vals, out, n, flip);
       break;
     case 1:
       hipLaunchKernelGGL(k_norm_small_int<int32_t>, dim3(g), dim3(THREADS), 0,
-                         stream, (const int32_t*)vals, out, n);
+                         stream, (const int32_t*)vals, out, n, flip);
       break;
     case 2:
       if (canonical)
         hipLaunchKernelGGL(k_norm_f64<true>, dim3(g), dim3(THREADS), 0,
-                           stream, (const double*)vals, out, n);
+                           stream, (const double*)vals, out, n, flip);
       else
         hipLaunchKernelGGL(k_norm_f64<false>, dim3(g), dim3(THREADS), 0,
-                           stream, (const double*)vals, out, n);
+                           stream, (const double*)vals, out, n, flip);
       break;
     case 3:
       if (canonical)
         hipLaunchKernelGGL(k_norm_f32<true>, dim3(g), dim3(THREADS), 0,
-                           stream, (const float*)vals, out, n);
+                           stream, (const float*)vals, out, n, flip);
       else
         hipLaunchKernelGGL(k_norm_f32<false>, dim3(g), dim3(THREADS), 0,
-                           stream, (const float*)vals, out, n);
+                           stream, (const float*)vals, out, n, flip);
       break;
     case 4:
       hipLaunchKernelGGL(k_norm_small_int<int16_t>, dim3(g), dim3(THREADS), 0,
-                         stream, (const int16_t*)vals, out, n);
+                         stream, (const int16_t*)vals, out, n, flip);
       break;
     case 5:
       hipLaunchKernelGGL(k_norm_small_int<int8_t>, dim3(g), dim3(THREADS), 0,
-                         stream, (const int8_t*)vals, out, n);
+                         stream, (const int8_t*)vals, out, n, flip);
       break;
     default:
       hipLaunchKernelGGL(k_norm_small_int<uint8_t>, dim3(g), dim3(THREADS),
-                         0, stream, (const uint8_t*)vals, out, n);
+                         0, stream, (const uint8_t*)vals, out, n, flip);
   }
 }
 
@@ -317,6 +324,13 @@ __global__ void k_xor_or_reduce(const uint64_t* __restrict__ keys, int64_t n,
   }
   if (threadIdx.x == 0)
     atomicOr((unsigned long long*)out_mask, (unsigned long long)lds[0]);
+}
+
+void key_varying_bits(const uint64_t* keys, int64_t n, uint64_t* d_mask,
+                      hipStream_t stream) {
+  if (n <= 0) return;
+  hipLaunchKernelGGL(k_xor_or_reduce, dim3(grid_for(n)), dim3(THREADS), 0,
+                     stream, keys, n, d_mask);
 }
 
 template <int RADIX>

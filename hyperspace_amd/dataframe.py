@@ -1,8 +1,8 @@
 """User-facing DataFrame: a logical plan + session.
 
 Mirrors the subset of the Spark DataFrame surface that Hyperspace's API
-touches: filter / select / join / group_by / agg / distinct / collect,
-plus plan access for
+touches: filter / select / join / group_by / agg / distinct / order_by /
+limit / collect, plus plan access for
 createIndex, explain and whyNot.
 """
 
@@ -11,8 +11,10 @@ from __future__ import annotations
 from typing import Dict, List, Optional, Union
 
 from .exceptions import HyperspaceException
-from .plan.expr import AggExpr, Col, Expr, col as _col, parse_predicate
-from .plan.nodes import Aggregate, Filter, Join, LogicalPlan, Project
+from .plan.expr import (AggExpr, Col, Expr, SortOrder, col as _col,
+                        parse_predicate)
+from .plan.nodes import (Aggregate, Filter, Join, Limit, LogicalPlan, Project,
+                         Sort)
 
 
 class DataFrame:
@@ -77,6 +79,55 @@ class DataFrame:
         aggregate expressions."""
         return DataFrame(self.session, Aggregate(
             self.plan.output_columns(), [], self.plan))
+
+    def order_by(self, *cols: Union[str, Col, SortOrder],
+                 ascending: Union[bool, List[bool]] = True) -> "DataFrame":
+        """Stable sort.  A column is a name, a ``Col`` or a ``SortOrder``
+        (``col("k").desc()``, ``F.asc_nulls_last("k")``); ``ascending`` (a
+        bool, or a list parallel to the columns) gives the direction of
+        the names and ``Col``s.  ASC puts nulls first and DESC last unless
+        the ``SortOrder`` says otherwise.  Values compare as in filters
+        and joins: NaN above every number, -0.0 with +0.0, strings
+        lexicographically.  Followed by ``limit(n)`` it runs as a top-n
+        selection and never sorts the whole input."""
+        if not cols:
+            raise HyperspaceException("order_by() needs at least one column")
+        if isinstance(ascending, (list, tuple)):
+            if len(ascending) != len(cols):
+                raise HyperspaceException(
+                    f"order_by(): {len(cols)} columns but "
+                    f"{len(ascending)} ascending flags")
+            flags = [bool(a) for a in ascending]
+        else:
+            flags = [bool(ascending)] * len(cols)
+        orders: List[SortOrder] = []
+        seen = set()
+        for c, asc in zip(cols, flags):
+            if isinstance(c, SortOrder):
+                o = c
+            elif isinstance(c, (str, Col)):
+                o = SortOrder(c, asc)
+            else:
+                raise HyperspaceException(
+                    f"order_by() takes names, Col or SortOrder, got {c!r}")
+            o = o.with_column(_resolve_columns(self.plan, [o.column])[0])
+            if o.column.lower() in seen:
+                raise HyperspaceException(
+                    f"Duplicate order column {o.column!r}")
+            seen.add(o.column.lower())
+            orders.append(o)
+        return DataFrame(self.session, Sort(orders, self.plan))
+
+    orderBy = order_by
+    sort = order_by
+
+    def limit(self, n: int) -> "DataFrame":
+        """The first ``n`` rows (``n = 0``: an empty batch with the
+        schema); after ``order_by`` the first ``n`` rows of that order."""
+        if isinstance(n, bool) or not isinstance(n, int) or n < 0:
+            raise HyperspaceException(
+                f"limit() takes a non-negative int, got {n!r}")
+        return DataFrame(self.session, Limit(n, self.plan))
 
     # -- actions ----------------------------------------------------------
     def optimized_plan(self) -> LogicalPlan:

@@ -14,6 +14,9 @@ Operator -> data-plane mapping:
   Aggregate       K13 group_offsets + fused segmented_reduce over adjacent
                       runs (no sort, no exchange, when the child is
                       bucketed on the grouping column)
+  Sort / Limit    K14 stable radix sort by order keys; Limit over Sort runs
+                      as a top-k: radix select of the candidates, or the
+                      heads of the buckets of an index on the order column
 """
 
 from __future__ import annotations
@@ -31,7 +34,8 @@ from ..exceptions import HyperspaceException
 from ..plan.expr import (And, BinComp, Col, Expr, In, IsNotNull, IsNull,
                          Lit, Not, Or, extract_equi_join_keys)
 from ..plan.nodes import (Aggregate, BucketUnionNode, Filter, IndexScan,
-                          Join, LogicalPlan, Project, Scan, UnionNode)
+                          Join, Limit, LogicalPlan, Project, Scan, Sort,
+                          UnionNode)
 from ..sources.parquet_io import (read_files_batch,
                                   read_files_batch_device,
                                   bucket_id_of_file)
@@ -48,6 +52,7 @@ class PhysicalStats:
         self.merge_joins = 0
         self.hash_joins = 0
         self.sort_aggregates = 0
+        self.sorts = 0             # full ORDER BY sorts (a top-k is none)
         self.bucket_pruned_files = 0
         self.operators: List[str] = []
 
@@ -93,6 +98,10 @@ class Executor:
             return self._exec_bucket_union(plan)
         if isinstance(plan, Aggregate):
             return self._exec_aggregate(plan), None
+        if isinstance(plan, Sort):
+            return self._exec_sort(plan), None
+        if isinstance(plan, Limit):
+            return self._exec_limit(plan), None
         if isinstance(plan, UnionNode):
             self.stats.record("Union")
             parts = [self._exec(c)[0] for c in plan.children]
@@ -705,6 +714,62 @@ class Executor:
         return _reduce_runs(batch, keys, plan.aggs)
 
     # ------------------------------------------------------------------
+    def _refuse_distributed_order(self, what: str):
+        from ..parallel import dist_context as dc
+        if dc.is_distributed() and dc.get_world_size() > 1:
+            raise HyperspaceException(
+                f"{what} is not supported in a distributed session: every "
+                "rank holds a partition of the rows, and a per-rank order "
+                "is not a global one")
+
+    def _exec_sort(self, plan: Sort) -> ColumnBatch:
+        """Full ORDER BY: gather by the stable multi-column permutation."""
+        from .ordering import order_perm
+        self._refuse_distributed_order("ORDER BY")
+        batch, _ = self._exec(plan.child)
+        self.stats.record("Sort")
+        self.stats.sorts += 1
+        if batch.num_rows > 1:
+            batch = batch.gather(order_perm(batch, plan.orders))
+        return batch
+
+    def _exec_limit(self, plan: Limit) -> ColumnBatch:
+        """LIMIT n: the child's first n rows; over a Sort (directly or
+        through one Project) a top-k that never sorts the whole input.
+
+        TopK(bucketed): one order column, and the child is bucketed and
+        sorted on it (no nulls in it): the first (last) n rows of every
+        bucket are the candidates.  TopK(select): everything else, by
+        radix select on the leading order column.  Both sort only their
+        candidates."""
+        from . import ordering
+        self._refuse_distributed_order("LIMIT")
+        sort, project = _limit_sort_shape(plan)
+        n = plan.n
+        if sort is None:
+            batch, _ = self._exec(plan.child)
+            self.stats.record("Limit")
+            return batch.slice(0, min(n, batch.num_rows))
+        batch, seg = self._exec(sort.child)
+        op = topk_operator_name(plan)
+        if op == "TopK(bucketed)" and (
+                seg is None or batch.has_nulls(sort.orders[0].column)):
+            # multi-file buckets re-sort on the stored placeholder of null
+            # rows: nulls are not reliably first there
+            op = "TopK(select)"
+        self.stats.record(op)
+        if n == 0 or batch.num_rows == 0:
+            out = batch.slice(0, 0)
+        elif op == "TopK(bucketed)":
+            out = ordering.topk_bucketed(batch, seg, sort.orders[0], n)
+        else:
+            out = ordering.topk_select(batch, sort.orders, n)
+        if project is not None:
+            self.stats.record("Project")
+            out = out.select(project.columns)
+        return out
+
+    # ------------------------------------------------------------------
     def _exec_bucket_union(self, plan: BucketUnionNode
                            ) -> Tuple[ColumnBatch, Optional[torch.Tensor]]:
         """Partition-aligned union: concatenate same-bucket segments from
@@ -926,6 +991,41 @@ def aggregate_operator_name(plan: Aggregate) -> str:
             _bucketed_group_source(plan.child, plan.group_cols[0]):
         return "SortAggregate(bucketed)"
     return "SortAggregate(shuffled)"
+
+
+def _limit_sort_shape(plan: Limit):
+    """(Sort, Project or None) when the Limit sits on a Sort, directly or
+    through one Project; (None, None) otherwise."""
+    node = plan.child
+    if isinstance(node, Sort):
+        return node, None
+    if isinstance(node, Project) and isinstance(node.child, Sort):
+        return node.child, node
+    return None, None
+
+
+def _bucketed_order_source(plan: LogicalPlan, key: str) -> bool:
+    """Like _bucketed_group_source, walked down through Project only: a
+    Filter drops the segment offsets, which the bucket heads come from."""
+    node = plan
+    while isinstance(node, Project):
+        node = node.child
+    return not isinstance(node, Filter) and _bucketed_group_source(node, key)
+
+
+def topk_operator_name(plan: Limit) -> str:
+    """Physical operator a Limit node runs as: ``Limit`` on its own, over
+    a Sort ``TopK(bucketed)`` when there is one order column and the
+    Sort's child is bucketed on it, else ``TopK(select)``.  (A bucketed
+    source whose key column holds nulls falls to the select at run
+    time.)"""
+    sort, _ = _limit_sort_shape(plan)
+    if sort is None:
+        return "Limit"
+    if len(sort.orders) == 1 and \
+            _bucketed_order_source(sort.child, sort.orders[0].column):
+        return "TopK(bucketed)"
+    return "TopK(select)"
 
 
 _REDUCE_OUTPUTS = {"sum": ("sum", "count"), "avg": ("sum", "count"),

@@ -1,4 +1,5 @@
-"""Aggregate functions for ``DataFrame.agg`` / ``GroupedData.agg``.
+"""Aggregate functions for ``DataFrame.agg`` / ``GroupedData.agg`` and
+sort orders for ``DataFrame.order_by``.
 
     from hyperspace_amd import functions as F
     df.group_by("k").agg(F.sum("a").alias("total"), F.count())
@@ -13,9 +14,10 @@ from __future__ import annotations
 
 from typing import Optional, Union
 
-from .plan.expr import AggExpr, Col
+from .plan.expr import AggExpr, Col, SortOrder
 
-__all__ = ["count", "sum", "min", "max", "avg"]
+__all__ = ["count", "sum", "min", "max", "avg",
+           "asc", "desc", "asc_nulls_last", "desc_nulls_first"]
 
 _ColLike = Union[str, Col]
 
@@ -47,3 +49,21 @@ def avg(col: _ColLike) -> AggExpr:
     this is the average of the UNSCALED integer values (the scale stays in
     the schema and is not applied)."""
     return AggExpr("avg", col)
+
+
+def asc(col: _ColLike) -> SortOrder:
+    """Ascending, nulls first (Spark's default for ASC)."""
+    return SortOrder(col, True)
+
+
+def desc(col: _ColLike) -> SortOrder:
+    """Descending, nulls last (Spark's default for DESC)."""
+    return SortOrder(col, False)
+
+
+def asc_nulls_last(col: _ColLike) -> SortOrder:
+    return SortOrder(col, True, False)
+
+
+def desc_nulls_first(col: _ColLike) -> SortOrder:
+    return SortOrder(col, False, True)

@@ -19,6 +19,8 @@ Op -> reference data-plane mapping:
   zorder_key       K10 z-address bit interleave
   group_offsets    K13 group-by: offsets of adjacent equal-key runs
   segmented_reduce K13 group-by: fused per-group sum/min/max/count
+  topk_rows        K14 ORDER BY ... LIMIT: radix select of the k smallest keys
+  order_key        K14 sql_key, complemented for a descending order
   (extension-only: copy_unaligned/rle_decode/snappy_decompress — the K1
   parquet page decode surface used by sources/parquet_io.py)
 """
@@ -37,7 +39,7 @@ __all__ = [
     "merge_join", "run_merge_perm", "select_range_u64", "isin_sorted", "segmented_minmax",
     "bloom_build", "bloom_probe", "bloom_probe_many", "zorder_key", "gather_rows", "native",
     "group_offsets", "segmented_reduce", "group_tile_size",
-    "bucket_sort_perm",
+    "bucket_sort_perm", "order_key", "topk_rows", "topk_tile_size",
 ]
 
 
@@ -54,6 +56,17 @@ def sql_key(col: torch.Tensor) -> torch.Tensor:
     if col.is_cuda:
         return native.ext().normalize_key(col.contiguous(), True)
     return cpu_ref.sql_key(col)
+
+
+def order_key(col: torch.Tensor, descending: bool = False) -> torch.Tensor:
+    """sql_key for an ORDER BY column: ascending u64 order of the result
+    is the requested order of the values.  Descending is the bitwise
+    complement of sql_key, taken in the same kernel pass."""
+    if col.is_cuda:
+        return native.ext().normalize_key(col.contiguous(), True,
+                                          bool(descending))
+    key = cpu_ref.sql_key(col)
+    return ~key if descending else key
 
 
 def gather_rows(values: torch.Tensor, idx: torch.Tensor) -> torch.Tensor:
@@ -214,6 +227,30 @@ def zorder_key(cols_u64: List[torch.Tensor], bits_per_col: int
 def group_tile_size() -> int:
     """Rows per tile of the device group-by kernels (tests aim at it)."""
     return int(native.ext().group_tile_size())
+
+
+def topk_tile_size() -> int:
+    """Rows per tile of the device top-k kernels (tests aim at it)."""
+    return int(native.ext().topk_tile_size())
+
+
+def topk_rows(keys_u64: torch.Tensor, k: int, valid=None,
+              keep_ties: bool = False) -> torch.Tensor:
+    """int64 row indices, ascending, of the rows holding the ``k`` smallest
+    keys (u64 order) among those with ``valid[i]`` true (all rows when
+    ``valid`` is None).  With T the k-th smallest such key: every valid row
+    below T, then of the rows equal to T all of them (``keep_ties``) or
+    the first k - #below in row order, so exactly min(k, n_valid) rows.
+    k <= 0 gives no row; the stored key of an invalid row is ignored.
+    On the device this is a radix select: no sort, one host read (the
+    output length)."""
+    k = min(int(k), keys_u64.numel())
+    if _is_cuda(keys_u64):
+        v = (valid.contiguous() if valid is not None
+             else torch.empty(0, dtype=torch.bool, device=keys_u64.device))
+        return native.ext().topk_rows(keys_u64.contiguous(), k, v,
+                                      bool(keep_ties))
+    return cpu_ref.topk_rows(keys_u64, k, valid, keep_ties)
 
 
 def group_offsets(keys: List[torch.Tensor], masks=None) -> torch.Tensor:

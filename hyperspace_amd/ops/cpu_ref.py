@@ -273,6 +273,35 @@ def select_range_u64(keys_u64: torch.Tensor, lo: int, hi: int,
     return torch.nonzero(m_lo & m_hi, as_tuple=False).flatten()
 
 
+def topk_rows(keys_u64: torch.Tensor, k: int,
+              valid: Optional[torch.Tensor] = None,
+              keep_ties: bool = False) -> torch.Tensor:
+    """Rows of the k smallest keys (u64 order) among the valid rows, in
+    ascending row index.  With T the k-th smallest valid key: every valid
+    row below T, then of the rows equal to T all of them (``keep_ties``)
+    or the first k - #below in row order.  k <= 0 gives no row, k >=
+    n_valid every valid row; the stored key of an invalid row is ignored."""
+    n = keys_u64.numel()
+    if valid is None:
+        valid = torch.ones(n, dtype=torch.bool, device=keys_u64.device)
+    valid = valid.to(torch.bool)
+    rows = torch.nonzero(valid, as_tuple=False).flatten()
+    if k <= 0 or rows.numel() == 0:
+        return rows[:0]
+    if k >= rows.numel():
+        return rows
+    s = _as_unsigned_sortable(keys_u64)
+    ordered, _ = torch.sort(s[rows], stable=True)
+    t = ordered[k - 1]
+    below = valid & (s < t)
+    ties = torch.nonzero(valid & (s == t), as_tuple=False).flatten()
+    if not keep_ties:
+        ties = ties[:k - int(below.sum())]
+    take = below.clone()
+    take[ties] = True
+    return torch.nonzero(take, as_tuple=False).flatten()
+
+
 def isin_sorted(values: torch.Tensor,
                 sorted_set: torch.Tensor) -> torch.Tensor:
     """Boolean mask: values ∈ sorted_set (both int64)."""

@@ -79,6 +79,19 @@ class Col(Expr):
     def is_null(self):
         return IsNull(self)
 
+    # sort orders (Spark: ASC is NULLS FIRST, DESC is NULLS LAST)
+    def asc(self):
+        return SortOrder(self.name, True)
+
+    def desc(self):
+        return SortOrder(self.name, False)
+
+    def asc_nulls_last(self):
+        return SortOrder(self.name, True, False)
+
+    def desc_nulls_first(self):
+        return SortOrder(self.name, False, True)
+
     def __hash__(self):
         return hash(("Col", self.name.lower()))
 
@@ -293,6 +306,35 @@ class AggExpr:
         if self.alias_name:
             return f"{self.default_name} AS {self.alias_name}"
         return self.default_name
+
+
+class SortOrder:
+    """One ORDER BY term: ``column`` ascending or descending, nulls first
+    or last.  ``nulls_first=None`` takes Spark's default: first for ASC,
+    last for DESC.  Built by ``Col.asc()`` / ``Col.desc()`` and the
+    ``hyperspace_amd.functions`` helpers; not a row-level ``Expr``."""
+
+    def __init__(self, column: "Union[str, Col]", ascending: bool = True,
+                 nulls_first: "Union[bool, None]" = None):
+        if isinstance(column, Col):
+            column = column.name
+        if not isinstance(column, str):
+            raise HyperspaceException(
+                f"SortOrder needs a column name, got {column!r}")
+        self.column = column
+        self.ascending = bool(ascending)
+        self.nulls_first = self.ascending if nulls_first is None \
+            else bool(nulls_first)
+
+    def with_column(self, column: str) -> "SortOrder":
+        return SortOrder(column, self.ascending, self.nulls_first)
+
+    def references(self) -> Set[str]:
+        return {self.column}
+
+    def __repr__(self):
+        return (f"{self.column} {'ASC' if self.ascending else 'DESC'} "
+                f"NULLS {'FIRST' if self.nulls_first else 'LAST'}")
 
 
 def col(name: str) -> Col:

@@ -15,7 +15,7 @@ from __future__ import annotations
 
 from typing import Any, Dict, List, Optional, Tuple
 
-from .expr import AggExpr, Expr
+from .expr import AggExpr, Expr, SortOrder
 from ..exceptions import HyperspaceException
 
 
@@ -207,6 +207,49 @@ class Aggregate(LogicalPlan):
         keys = ", ".join(self.group_cols)
         aggs = ", ".join(repr(a) for a in self.aggs)
         return f"Aggregate(keys=[{keys}], [{aggs}])"
+
+
+class Sort(LogicalPlan):
+    """Order ``child`` by ``orders`` (SortOrder terms, most significant
+    first).  Stable: rows that tie on every term keep the child's order."""
+
+    def __init__(self, orders: List[SortOrder], child: LogicalPlan):
+        super().__init__([child])
+        self.orders = list(orders)
+
+    @property
+    def child(self):
+        return self.children[0]
+
+    def output_columns(self):
+        return self.child.output_columns()
+
+    def with_children(self, children):
+        return Sort(self.orders, children[0])
+
+    def _node_str(self):
+        return "Sort([" + ", ".join(repr(o) for o in self.orders) + "])"
+
+
+class Limit(LogicalPlan):
+    """The first ``n`` rows of ``child``."""
+
+    def __init__(self, n: int, child: LogicalPlan):
+        super().__init__([child])
+        self.n = n
+
+    @property
+    def child(self):
+        return self.children[0]
+
+    def output_columns(self):
+        return self.child.output_columns()
+
+    def with_children(self, children):
+        return Limit(self.n, children[0])
+
+    def _node_str(self):
+        return f"Limit({self.n})"
 
 
 class IndexScan(LogicalPlan):

@@ -9,7 +9,7 @@ from __future__ import annotations
 
 from typing import Dict, List
 
-from ..plan.nodes import Aggregate, IndexScan, LogicalPlan
+from ..plan.nodes import Aggregate, IndexScan, Limit, LogicalPlan
 from ..rules.apply_hyperspace import ApplyHyperspace
 from ..rules.filter_reason import ReasonCollector
 
@@ -38,6 +38,12 @@ def _operator_counts(plan: LogicalPlan) -> Dict[str, int]:
             from ..execution.executor import aggregate_operator_name
             phys = aggregate_operator_name(n)
             counts[phys] = counts.get(phys, 0) + 1
+        elif isinstance(n, Limit):
+            # a Limit over a Sort runs as one of the top-k operators
+            from ..execution.executor import topk_operator_name
+            phys = topk_operator_name(n)
+            if phys != "Limit":
+                counts[phys] = counts.get(phys, 0) + 1
         for c in n.children:
             walk(c)
 

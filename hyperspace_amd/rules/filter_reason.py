@@ -26,6 +26,7 @@ class FilterReasons:
     ANOTHER_INDEX_APPLIED = "ANOTHER_INDEX_APPLIED"
     NO_FILTER_ON_INDEXED_COL = "NO_FILTER_ON_INDEXED_COL"
     GROUP_COLS_NOT_INDEXED_COL = "GROUP_COLS_NOT_INDEXED_COL"
+    SORT_COL_NOT_INDEXED_COL = "SORT_COL_NOT_INDEXED_COL"
 
 
 @dataclass

@@ -1,5 +1,5 @@
 """The rewrite rules: FilterIndexRule, JoinIndexRule, AggregateIndexRule,
-NoOpRule.
+TopKIndexRule, NoOpRule.
 
 Reference:
   - HyperspaceRule template  index/rules/HyperspaceRule.scala:28-91
@@ -17,6 +17,10 @@ Reference:
     spec matches the grouping keys; here the rule exposes that layout
     (single-column covering index == the grouping column; score = 70 ×
     coverage, the per-side join score)
+  - TopKIndexRule has none either: Spark would sort every partition and
+    take the head of each; here the buckets of an index on the order
+    column are sorted already, so only their heads are read (score = 50 ×
+    coverage, the filter rule's weight: one scan is replaced)
 """
 
 from __future__ import annotations
@@ -28,7 +32,8 @@ from .candidate_collector import (Candidate, TAG_APPENDED_FILES,
 from .filter_reason import FilterReason, FilterReasons, ReasonCollector
 from ..plan.expr import extract_equi_join_keys
 from ..plan.nodes import (Aggregate, BucketUnionNode, Filter, IndexScan,
-                          Join, LogicalPlan, Project, Scan, UnionNode)
+                          Join, Limit, LogicalPlan, Project, Scan, Sort,
+                          UnionNode)
 
 
 class HyperspaceRule:
@@ -396,3 +401,78 @@ class AggregateIndexRule(HyperspaceRule):
             index_names=[best.name], message="AggregateIndexRule applied"))
         return (Aggregate(plan.group_cols, plan.aggs, child),
                 self.SCORE * _coverage(best))
+
+
+class TopKIndexRule(HyperspaceRule):
+    """Serve ``ORDER BY col LIMIT n`` from a covering index bucketed and
+    sorted on ``col``: the answer lies in the first (descending: last) n
+    rows of the buckets, so the executor never reads the column in full.
+    The Sort and Limit nodes stay; only the scan below them is replaced.
+
+    A Filter below the Sort is left to the filter rules: it drops the
+    bucket offsets the heads are taken from.  Multi-column indexes are
+    excluded for the reason AggregateIndexRule gives."""
+    name = "TopKIndexRule"
+    SCORE = 50.0
+
+    def apply(self, plan, candidates):
+        if not isinstance(plan, Limit) or \
+                not self.session.conf.topk_rule_enabled:
+            return plan, 0.0
+        outer = None
+        sort = plan.child
+        if isinstance(sort, Project):
+            outer, sort = sort, sort.child
+        if not isinstance(sort, Sort) or len(sort.orders) != 1:
+            return plan, 0.0
+        shape = _decompose_linear(sort.child)
+        if shape is None:
+            return plan, 0.0
+        project, filt, scan = shape
+        if filt is not None:
+            return plan, 0.0
+        cands = candidates.get(id(scan), [])
+        if not cands:
+            return plan, 0.0
+        order_col = sort.orders[0].column
+        if project is not None:
+            needed = _needed_columns(project, None, scan)
+        elif outer is not None:
+            # only what the projection above the sort keeps, and the
+            # order column
+            needed = list(outer.columns)
+            if order_col.lower() not in {c.lower() for c in needed}:
+                needed.append(order_col)
+        else:
+            needed = _needed_columns(None, None, scan)
+        eligible: List[Candidate] = []
+        for cand in cands:
+            index = cand.index
+            if index.kind != "CoveringIndex":
+                continue
+            if [c.lower() for c in index.indexed_columns] != \
+                    [order_col.lower()]:
+                self.reasons.add(cand.name, plan, FilterReason(
+                    FilterReasons.SORT_COL_NOT_INDEXED_COL,
+                    {"sortCol": order_col,
+                     "indexedCols": str(index.indexed_columns)}))
+                continue
+            covered = {c.lower() for c in index.referenced_columns()}
+            if not {c.lower() for c in needed} <= covered:
+                self.reasons.add(cand.name, plan, FilterReason(
+                    FilterReasons.MISSING_REQUIRED_COL,
+                    {"needed": str(needed)}))
+                continue
+            eligible.append(cand)
+        if not eligible:
+            return plan, 0.0
+        best = _rank_by_size(eligible)
+        child = _rewrite_bucketed_side(best, scan, project, None, needed)
+        self.reasons.applied.setdefault(best.name, []).append(self.name)
+        from ..telemetry import HyperspaceIndexUsageEvent
+        self.session.event_logger.log_event(HyperspaceIndexUsageEvent(
+            index_names=[best.name], message="TopKIndexRule applied"))
+        new_plan: LogicalPlan = Sort(sort.orders, child)
+        if outer is not None:
+            new_plan = Project(outer.columns, new_plan)
+        return Limit(plan.n, new_plan), self.SCORE * _coverage(best)

@@ -13,7 +13,8 @@ from typing import Dict, List, Tuple
 from .candidate_collector import Candidate
 from .filter_reason import ReasonCollector
 from .hyperspace_rules import (AggregateIndexRule, FilterIndexRule,
-                               HyperspaceRule, JoinIndexRule, NoOpRule)
+                               HyperspaceRule, JoinIndexRule, NoOpRule,
+                               TopKIndexRule)
 from ..plan.nodes import LogicalPlan
 
 
@@ -25,6 +26,7 @@ class ScoreBasedIndexPlanOptimizer:
             FilterIndexRule(session, reasons),
             JoinIndexRule(session, reasons),
             AggregateIndexRule(session, reasons),
+            TopKIndexRule(session, reasons),
         ]
         # secondary index kinds participate when present
         try:

@@ -29,6 +29,7 @@ setup(
                 "hyperspace_amd/csrc/bucket_writer.cpp",
                 "hyperspace_amd/csrc/kernels/kernels.hip",
                 "hyperspace_amd/csrc/kernels/aggregate.hip",
+                "hyperspace_amd/csrc/kernels/topk.hip",
             ],
             include_dirs=[os.path.join(ROOT, "hyperspace_amd", "csrc")],
             extra_compile_args={
