@@ -355,3 +355,75 @@ class ColumnBatch:
             parts.append(f"{k}:{kind}")
         return (f"ColumnBatch[{self._num_rows} rows, "
                 f"{', '.join(parts)}, dev={self.device}]")
+
+
+# ---------------------------------------------------------------------------
+# batch constructors
+# ---------------------------------------------------------------------------
+
+_SPARK_DTYPES = {"long": torch.int64, "integer": torch.int32,
+                 "short": torch.int16, "byte": torch.int8,
+                 "date": torch.int32,  # days; hashes as int, like Spark
+                 "double": torch.float64, "float": torch.float32}
+
+
+def _empty_batch(schema) -> ColumnBatch:
+    """Zero-row batch carrying the relation's column structure (empty
+    shards in a distributed scan must keep the schema)."""
+    cols: Dict[str, object] = {}
+    for f in schema.fields:
+        if f.type == "string":
+            cols[f.name] = StringColumn(
+                torch.empty(0, dtype=torch.int32), [])
+        else:
+            dt = _SPARK_DTYPES.get(f.type, torch.int64)
+            cols[f.name] = torch.empty(0, dtype=dt)
+    return ColumnBatch(cols)
+
+
+def _null_batch(like: ColumnBatch, n: int) -> ColumnBatch:
+    """``n`` all-null rows with the columns and dtypes of ``like``.  The
+    value slots hold the fill a null carries elsewhere (0 / the first
+    dictionary entry, "" for an empty dictionary)."""
+    dev = like.device
+    cols: Dict[str, object] = {}
+    for k, v in like.columns.items():
+        if isinstance(v, StringColumn):
+            cols[k] = StringColumn(
+                torch.zeros(n, dtype=torch.int32, device=dev),
+                v.values if len(v.values) else [""])
+        else:
+            cols[k] = torch.zeros(n, dtype=v.dtype, device=dev)
+    return ColumnBatch(cols, {k: torch.zeros(n, dtype=torch.bool, device=dev)
+                              for k in cols})
+
+
+def _gather_nullable(batch: ColumnBatch, idx: torch.Tensor) -> ColumnBatch:
+    """Gather where ``idx == -1`` yields an all-null row.  The -1 never
+    reaches the gather: it is clamped to row 0 and masked out; a batch
+    with no rows to clamp to is built as nulls directly."""
+    if batch.num_rows == 0:
+        return _null_batch(batch, idx.numel())
+    out = batch.gather(idx.clamp_min(0))
+    valid = idx >= 0
+    masks = {}
+    for k in out.columns:
+        m = out.mask(k)
+        masks[k] = valid if m is None else (valid & m)
+    return ColumnBatch(out.columns, masks)
+
+
+def _join_columns(lout: ColumnBatch, rout: ColumnBatch) -> ColumnBatch:
+    """Left then right columns; a right name already taken gets ``_r``."""
+    cols: Dict[str, object] = {}
+    masks: Dict[str, torch.Tensor] = {}
+    for k, v in lout.columns.items():
+        cols[k] = v
+        if lout.mask(k) is not None:
+            masks[k] = lout.mask(k)
+    for k, v in rout.columns.items():
+        name = k if k not in cols else f"{k}_r"
+        cols[name] = v
+        if rout.mask(k) is not None:
+            masks[name] = rout.mask(k)
+    return ColumnBatch(cols, masks)

@@ -97,8 +97,6 @@ class ScanStream:
     def materialize(self) -> ColumnBatch:
         parts = list(self.batches())
         if not parts:
-            from ..execution.executor import _empty_batch
-            from ..log.entry import Schema, SchemaField
             return ColumnBatch({})
         if len(parts) == 1:
             return parts[0]

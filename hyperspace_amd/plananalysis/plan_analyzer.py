@@ -9,6 +9,7 @@ from __future__ import annotations
 
 from typing import Dict, List
 
+from ..execution.layout import aggregate_operator_name, topk_operator_name
 from ..plan.nodes import Aggregate, IndexScan, Limit, LogicalPlan
 from ..rules.apply_hyperspace import ApplyHyperspace
 from ..rules.filter_reason import ReasonCollector
@@ -35,12 +36,10 @@ def _operator_counts(plan: LogicalPlan) -> Dict[str, int]:
         counts[name] = counts.get(name, 0) + 1
         if isinstance(n, Aggregate):
             # the physical operator the aggregate runs as
-            from ..execution.executor import aggregate_operator_name
             phys = aggregate_operator_name(n)
             counts[phys] = counts.get(phys, 0) + 1
         elif isinstance(n, Limit):
             # a Limit over a Sort runs as one of the top-k operators
-            from ..execution.executor import topk_operator_name
             phys = topk_operator_name(n)
             if phys != "Limit":
                 counts[phys] = counts.get(phys, 0) + 1

@@ -553,7 +553,7 @@ def scenario_bucketed(env, index_col="i"):
 def scenario_bucketed_nullable_key(env):
     """An index on a key with nulls: planned as TopK(bucketed), run as
     TopK(select), and right."""
-    from hyperspace_amd.execution.executor import topk_operator_name
+    from hyperspace_amd.execution.layout import topk_operator_name
     env.session.enable_hyperspace()
     for asc, nulls_first in DIRECTIONS:
         orders = [("n32", asc, nulls_first)]
